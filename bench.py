@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 GOLD = os.path.join(ROOT, "tests", "golden", "data")
 STUB = os.environ.get("BRX_BENCH_STUB") == "1"  # CPU test of the launcher path only (tests/test_bench_launch.py)
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak
 
 C5 = os.path.join(ROOT, "tests", "golden", "config5")
 WORKLOADS = {
@@ -389,6 +389,29 @@ def timed_pass(ctx, batch, steps, warmup, barrier):
     return time.perf_counter() - t0, kernel_ms
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much
+
+
+def dump_outputs(path, torch, np, slots, out_len, status):
+    """--dump-outputs: what a caller of the timed path received from its last step, so that two builds can be compared output for
+    output.  slots: the [n, capacity] uint8 output slots (torch, any device); out_len / status: numpy arrays of n.  Writes
+      status.npy, out_len.npy   every stream's (float64)
+      sample_streams.npy        a fixed, seeded sample of stream indices -- as many as DUMP_BYTES leaves room for (float64)
+      out_bytes.npy             [sample, capacity]: byte j of a sampled stream's slot for j < min(out_len, capacity) (brx.h: the
+                                stream's output, or the bytes in front of its error), -1 behind it (float32)"""
+    n, cap = slots.shape
+    lens = np.asarray(out_len, dtype=np.float64)
+    room = (DUMP_BYTES - 3 * 8 * n - 4 * 128) // 4  # float32 bytes left after the three per-stream arrays and the four .npy headers
+    width = min(cap, room)
+    pick = np.sort(np.random.default_rng(0).choice(n, min(n, room // width), replace=False))
+    got = slots[torch.from_numpy(pick).to(slots.device), :width].cpu().numpy().astype(np.float32)
+    got[np.arange(width)[None, :] >= np.minimum(lens[pick], cap)[:, None]] = -1.0
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("status", np.asarray(status, dtype=np.float64)), ("out_len", lens), ("sample_streams", pick.astype(np.float64)),
+                    ("out_bytes", got)):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def copy_path(torch, np, dev, ctx, barrier, steps=5):
     """The LZ77 copy path in the driver-run line (north_star: the copy at >= 40 % of HBM peak): three short runs with the
     PHYSICAL bytes known by construction -- far copies HBM -> registers -> HBM (every copied byte read once), the two
@@ -548,8 +571,12 @@ def node_main(args):
     last = node.last()
     if args.node == "host":
         st, ln = r
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, torch, np, torch.from_numpy(hout[:N * b.cap]).view(N, b.cap), ln, st)
         ok = (not st.any()) and all(hout[i * b.cap:i * b.cap + len(fx[i % len(fx)][1])].tobytes() == fx[i % len(fx)][1] for i in (0, N // 2, N - 1))
     else:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, torch, np, b.out.view(N, b.cap), b.out_len.cpu().numpy(), b.status.cpu().numpy())
         ok = b.verify(torch)
     res = {"metric": "decompressed MB/s (whole node), %s batch, single process through brx_node_decode_batch (%s pointers)" % (args.workload, args.node),
            "value": round(b.out_bytes * args.steps / dt / 1e6, 1), "unit": "MB/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
@@ -585,7 +612,11 @@ def main():
     ap.add_argument("--node", choices=["host", "device"], default=None, help="ONE process for all N GPUs through brx_node_decode_batch (the C ABI's node entry) instead of one rank per GPU")
     ap.add_argument("--deal", choices=["ranges", "bytes", "snake"], default="ranges", help="--node: how the batch is dealt over the GPUs")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (config 5's per-GPU share, the cut-stream batch) and `node_abi`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0's batch; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the last timed step is the one verified and dumped)")
 
     if args.node and not STUB:
         node_main(args)  # does not return
@@ -664,6 +695,8 @@ def main():
         return [float(v.item()) for v in ts]
 
     dt, kernel_ms = timed_pass(ctx, batch, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, batch.out.view(n, batch.cap), batch.out_len.cpu().numpy(), batch.status.cpu().numpy())
     dt = max_over_ranks(dt)
     kavg = sum(kernel_ms) / max(len(kernel_ms), 1)
     kavg_ranks = all_ranks(kavg)

@@ -94,3 +94,53 @@ open(os.path.join(d, "host", "123", "p_counter_collection.csv"), "w").write("\\n
     assert not bench.under_profiler()
     monkeypatch.setenv("ROCPROF_OUTPUT_PATH", "/tmp/x")
     assert bench.under_profiler()
+
+
+def test_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: the slots, lengths and status the last timed step left (the stand-in decode writes the fixture's bytes),
+    the same from run to run; --steps is the number of timed steps and must be at least 1."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("d%d" % k)
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "monkeyx16384", "--streams", "8", "--dump-outputs", str(d)], stub=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["steps"] == 3
+        runs.append({n: np.load(d / (n + ".npy")) for n in ("status", "out_len", "sample_streams", "out_bytes")})
+    a, b = runs
+    assert all(np.array_equal(a[n], b[n]) and a[n].dtype == b[n].dtype for n in a)
+    want = np.frombuffer(open(os.path.join(ROOT, "tests", "golden", "data", "monkey"), "rb").read(), dtype=np.uint8)
+    assert a["out_bytes"].dtype == np.float32 and a["out_len"].dtype == np.float64
+    assert (a["status"] == 0).all() and (a["out_len"] == len(want)).all() and (a["sample_streams"] == np.arange(8)).all()
+    assert (a["out_bytes"][:, :len(want)] == want).all() and (a["out_bytes"][:, len(want):] == -1).all()
+    r = _run(["--gpus", "1", "--steps", "0", "--warmup", "1", "--dump-outputs", str(tmp_path / "none")], stub=True)
+    assert r.returncode != 0 and not any(l.startswith("{") for l in r.stdout.splitlines()) and not (tmp_path / "none").exists()
+
+
+def test_dump_outputs_samples_a_large_batch_within_64_MB(tmp_path):
+    """A batch whose slots exceed the budget: a fixed, seeded sample of whole streams, each slot's bytes up to min(out_len, capacity)
+    and -1 behind (statuses other than 0 keep the bytes in front of the error, brx.h), at most 64 MB in all."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, cap = 600, 152096
+    g = torch.Generator().manual_seed(5)
+    slots = torch.randint(0, 256, (n, cap), dtype=torch.uint8, generator=g)
+    out_len = np.random.default_rng(5).integers(0, 2 * cap, n).astype(np.uint64)
+    status = np.where(out_len > cap, 25, 0).astype(np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch, np, slots, out_len, status)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["out_bytes.npy", "out_len.npy", "sample_streams.npy", "status.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    pick = np.load(tmp_path / "a" / "sample_streams.npy").astype(np.int64)
+    got = np.load(tmp_path / "a" / "out_bytes.npy")
+    assert 50 < len(pick) < n and (np.diff(pick) > 0).all() and got.shape == (len(pick), cap)
+    assert np.array_equal(np.load(tmp_path / "a" / "out_len.npy"), out_len.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), status.astype(np.float64))
+    for row, i in zip(got, pick):
+        m = min(int(out_len[i]), cap)
+        assert (row[:m] == slots[i, :m].numpy()).all() and (row[m:] == -1).all()

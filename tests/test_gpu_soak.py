@@ -2,7 +2,7 @@
 output slot, c8bba1d) was found by tools/wide_fuzz.py on the builder's metered GPU, not by `pytest -m gpu`: the fuzzers of
 tools/gpu_soak_r04.sh run here as fixed-seed, time-boxed sections -- HIP path against the oracle / the original bytes, both launch
 plans, both builds of the assembly loop, a small slab pool.  Reference practice mirrored: the AFL findings of
-/root/reference/docs/notes_afl.txt:14-20 became the regression tests of tests/lib.rs:379-605.
+the reference's docs/notes_afl.txt:14-20 became the regression tests of tests/lib.rs:379-605.
 
 Each section is one fresh process (the A/B knobs reach the library through tests/brx_knobs.py from the process environment; the
 library itself reads none).  A section fails on any MISMATCH line or a non-zero exit."""
@@ -89,6 +89,10 @@ def test_soak_sections(group):
 
 
 KNOBS = ["BRX_PLAN_B=1", "BRX_PLAN_A=1", "BRX_LOOP_BUILD=1"]
+# suites running at once: each has the GPU open, as has this process and, at times, one child of each suite (a C++ test, a fresh
+# Python check) -- at most 1 + 2 x 2 = 5 processes with the GPU open (all three at once made 7, more than a GPU machine shared with
+# other jobs may be asked to hold)
+AT_ONCE = 2
 
 
 @pytest.mark.timeout(1200)
@@ -96,44 +100,45 @@ def test_parity_suite_again_under_forced_knobs():
     """tests/test_gpu_parity.py once more per knob, in fresh processes, with one A/B knob forced on every context the suite makes through
     tests/brx_knobs.py: launch plan B (classification pre-pass, all instances resident at once) on EVERY launch -- plan A decides by
     the context's history --, plan A only, and the sparse-launch build of the assembly loop (the tree cache of many-tree meta-blocks,
-    bit window in SGPRs) on full launches too.  Round 4 ran these by hand (profiles/r04_suite_forced.txt); round 6 runs the three
-    at the same time (BRX_SUITE_CONCURRENT=1 tells the few tests that assert on kernel TIMES to leave that assertion out)."""
-    procs = []
+    bit window in SGPRs) on full launches too.  Round 4 ran these by hand (profiles/r04_suite_forced.txt); they run AT_ONCE at a time
+    (BRX_SUITE_CONCURRENT=1 tells the few tests that assert on kernel TIMES to leave that assertion out)."""
     # (the launch plan never reaches the resumable decode of a reader -- one stream, its own launch: the plan knobs' re-runs leave the
     # reader tests out, the loop-build knob's keeps them)
     readers = "not pulled_reader and not bounded and not every_vector and not taken_back and not makes_room and not format_errors and not streaming_mode"
-    for knob in KNOBS:
-        name, value = knob.split("=")
-        full = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BRX_SUITE_CONCURRENT="1", **{name: value})
-        sel = ["-k", readers] if name.startswith("BRX_PLAN") else []
-        procs.append((knob, subprocess.Popen([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q",
-                                              "-p", "no:cacheprovider"] + sel, env=full, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT)))
     failed = []
-    for knob, p in procs:
-        try:
-            out, err = p.communicate(timeout=1100)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            out, err = p.communicate()
-            failed.append((knob, "TIMEOUT", out[-1500:]))
-            continue
-        if p.returncode != 0:
-            # (three suites share the GPU here: a failure is taken seriously only if the knob's suite also fails ALONE)
+    for wave in [KNOBS[i:i + AT_ONCE] for i in range(0, len(KNOBS), AT_ONCE)]:
+        procs = []
+        for knob in wave:
             name, value = knob.split("=")
-            alone = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"],
-                                   env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **{name: value}), capture_output=True, text=True, timeout=1000, cwd=ROOT)
-            if alone.returncode == 0:
-                try:
+            full = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BRX_SUITE_CONCURRENT="1", **{name: value})
+            sel = ["-k", readers] if name.startswith("BRX_PLAN") else []
+            procs.append((knob, subprocess.Popen([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q",
+                                                  "-p", "no:cacheprovider"] + sel, env=full, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT)))
+        for knob, p in procs:
+            try:
+                out, err = p.communicate(timeout=1100)
+            except subprocess.TimeoutExpired:
+                p.kill()
+                out, err = p.communicate()
+                failed.append((knob, "TIMEOUT", out[-1500:]))
+                continue
+            if p.returncode != 0:
+                # (AT_ONCE suites share the GPU here: a failure is taken seriously only if the knob's suite also fails ALONE)
+                name, value = knob.split("=")
+                alone = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"],
+                                       env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **{name: value}), capture_output=True, text=True, timeout=1000, cwd=ROOT)
+                if alone.returncode == 0:
+                    try:
+                        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+                        open(os.path.join(ROOT, "gpurun_out", "forced_knob_%s_concurrent_only.log" % knob.replace("=", "_")), "w").write(out + "\n---- stderr ----\n" + err)
+                    except OSError:
+                        pass
+                    continue
+                out, err = alone.stdout, alone.stderr
+                failed.append((knob, p.returncode, out[-3000:] + err[-1000:]))
+                try:  # (the assertion's repr cuts the text short: the whole log goes where gpurun brings it back from)
                     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-                    open(os.path.join(ROOT, "gpurun_out", "forced_knob_%s_concurrent_only.log" % knob.replace("=", "_")), "w").write(out + "\n---- stderr ----\n" + err)
+                    open(os.path.join(ROOT, "gpurun_out", "forced_knob_%s.log" % knob.replace("=", "_")), "w").write(out + "\n---- stderr ----\n" + err)
                 except OSError:
                     pass
-                continue
-            out, err = alone.stdout, alone.stderr
-            failed.append((knob, p.returncode, out[-3000:] + err[-1000:]))
-            try:  # (the assertion's repr cuts the text short: the whole log goes where gpurun brings it back from)
-                os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-                open(os.path.join(ROOT, "gpurun_out", "forced_knob_%s.log" % knob.replace("=", "_")), "w").write(out + "\n---- stderr ----\n" + err)
-            except OSError:
-                pass
     assert not failed, failed

@@ -1,8 +1,8 @@
 """The node in the C ABI (brx_node_*, include/brx.h): one process, one context and one host thread per GPU, a batch dealt
 over them.  CPU tests: the dealing (brx_node_deal) against shard.py's, which the gloo tests cover.  GPU tests: 2 .. 4 VIRTUAL ranks
-(contexts on device 0: the same code as on four GPUs -- threads, dealing, scatter, gather -- on the one GPU a gpurun box has),
+(contexts on device 0: the same code as on four GPUs -- threads, dealing, scatter, gather -- on a machine with one GPU),
 bit-exact against the oracle through host pointers, device pointers with peer copies, and RCCL at world size 1 (the root's shard sent to
-itself); the two-GPU test runs wherever two GPUs exist."""
+itself); the two-rank test puts its ranks on two GPUs wherever two exist, and RCCL between them."""
 import hashlib
 import json
 import os
@@ -322,11 +322,12 @@ def test_bad_arguments_are_refused_not_run():
 
 @pytest.mark.gpu
 def test_two_real_gpus_with_rccl():
-    """shard.py's world-2 test in the C ABI: needs two GPUs (the driver's 8-GPU node; skipped on a gpurun box)."""
+    """shard.py's world-2 test in the C ABI: a node of two ranks, host pointers, then device pointers exchanged by peer copies and by
+    RCCL under both deals.  With two GPUs the ranks are GPUs 0 and 1.  With one they share it: the peer-copy exchange runs as on two,
+    and RCCL, which cannot serve two ranks on one GPU, is refused with an error before anything runs -- the node decodes on after it."""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
-    node = brx.Node([0, 1])
+    two = torch.cuda.device_count() >= 2
+    node = brx.Node([0, 1] if two else [0, 0])
     try:
         streams, caps, _ = _fixture_batch()
         n = len(streams)
@@ -336,6 +337,10 @@ def test_two_real_gpus_with_rccl():
         for deal in ("ranges", "snake"):
             for transport in (1, 2):
                 node.set_option("transport", transport)
+                if transport == 2 and not two:
+                    with pytest.raises(brx.BrxError, match="RCCL needs every rank on a GPU of its own"):
+                        _run_device(node, t, n, deal=deal, use_gpus=2)
+                    continue
                 out, status, out_len = _run_device(node, t, n, deal=deal, use_gpus=2)
                 outs = [out[int(out_off[i]):int(out_off[i]) + int(out_len[i])].tobytes() if status[i] == 0 else b"" for i in range(n)]
                 _check_fixture_results(outs, status, out_len)

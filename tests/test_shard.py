@@ -3,8 +3,8 @@ compressed shards, local decode through the device-batch signature, ragged gathe
 
 CPU (not gpu): world_size 2 over gloo with CPU tensors; the decode in the middle is a stand-in with exactly the
 signature of the HIP path (flat tensors + offset tables, results written in place) that calls the oracle -- tests may
-use it as the checker.  GPU: the same functions with `shard.hip_decode_fn` (the HIP path): world 1 on any box, world 2
-over RCCL when the box has two GPUs."""
+use it as the checker.  GPU: the same functions with `shard.hip_decode_fn` (the HIP path): world 1 on any machine, world 2
+over RCCL when the machine has two GPUs (with one, both ranks decode on it and exchange over gloo)."""
 import json
 import os
 import socket
@@ -51,6 +51,16 @@ def _oracle_decode_fn():
     return fn
 
 
+def _on_gpu0(decode_fn):
+    """A device decode_fn for a shard held in host tensors: the shard to GPU 0, decode_fn there, its results back in place."""
+    def fn(in_t, in_off_t, n, out_t, out_off_t, out_len_t, status_t):
+        d = [x.to("cuda:0") for x in (in_t, in_off_t, out_t, out_off_t, out_len_t, status_t)]
+        decode_fn(d[0], d[1], n, d[2], d[3], d[4], d[5])
+        for host, dev in ((out_t, d[2]), (out_len_t, d[4]), (status_t, d[5])):
+            host.copy_(dev.cpu())
+    return fn
+
+
 def _check(names, data, offs, st):
     from brotli_rs_amd import shard
     outs = shard.unpack(data, offs)
@@ -73,7 +83,7 @@ def _worker(rank, world, port, result_path, backend, balance=False):
         torch.cuda.set_device(rank)
         dev = torch.device("cuda", rank)
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-    else:
+    else:  # "gloo", and "gloo_hip": host tensors between the ranks, the HIP decode on GPU 0 in the middle
         dev = torch.device("cpu")
         dist.init_process_group("gloo", rank=rank, world_size=world)
     from brotli_rs_amd import shard
@@ -87,6 +97,9 @@ def _worker(rank, world, port, result_path, backend, balance=False):
         from brotli_rs_amd import brx
         ctx = brx.Context(rank)
         fn = shard.hip_decode_fn(ctx)
+    elif backend == "gloo_hip":
+        from brotli_rs_amd import brx
+        fn = _on_gpu0(shard.hip_decode_fn(brx.Context(0)))
     else:
         fn = _oracle_decode_fn()
     out, out_offs, st = shard.decode_sharded(data, offs, caps, fn, src=0, device=dev, balance=balance)
@@ -190,9 +203,11 @@ def test_sharded_decode_hip_path_world1(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_sharded_decode_hip_path_world2_rccl(tmp_path):
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs (the driver's multi-GPU tier)")
+    """World 2 with the HIP decode on every rank.  Two GPUs: over RCCL, each rank decoding on a GPU of its own.  One GPU: RCCL cannot
+    serve two ranks on one GPU, so both ranks decode on it and the scatter / gather go over gloo with host tensors (each shard copied
+    to the GPU and its results back) -- the same sharding, slots, HIP decode and gather as on two."""
     port = _free_port()
     result = str(tmp_path / "result.txt")
-    mp.spawn(_worker, args=(2, port, result, "nccl"), nprocs=2, join=True)
+    backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo_hip"
+    mp.spawn(_worker, args=(2, port, result, backend), nprocs=2, join=True)
     assert open(result).read() == "ok"

@@ -1,8 +1,9 @@
-import sys, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os, sys, time
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
 from brotli_rs_amd import brx
 import brx_knobs  # noqa: E402
-G='/root/repo/tests/golden/data/'
+G=os.path.join(R, 'tests', 'golden', 'data') + '/'
 small=open(G+'monkey.compressed','rb').read(); exp=open(G+'monkey','rb').read()
 ctx=brx_knobs.context(0)
 for n in (65536, 262144):

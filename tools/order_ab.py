@@ -1,8 +1,9 @@
 import os, sys, time, json
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
 from brotli_rs_amd import brx
 import brx_knobs  # noqa: E402
-G='/root/repo/tests/golden'
+G=os.path.join(R, 'tests', 'golden')
 man=json.load(open(G+'/config5/manifest.json'))['streams']
 big=[open(G+'/config5/%s.compressed'%e['name'],'rb').read() for e in man]
 small=open(G+'/data/alice29.txt.compressed','rb').read()
