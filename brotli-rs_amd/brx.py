@@ -91,6 +91,10 @@ def load_library():
     L.brx_stream_read.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     L.brx_stream_free.restype = None
     L.brx_stream_free.argtypes = [ctypes.c_void_p]
+    L.brx_stream_advance.restype = ctypes.c_int
+    L.brx_stream_advance.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32]
+    L.brx_stream_ready.restype = ctypes.c_int64
+    L.brx_stream_ready.argtypes = [ctypes.c_void_p]
     L.brx_host_alloc.restype = ctypes.c_void_p
     L.brx_host_alloc.argtypes = [ctypes.c_size_t]
     L.brx_host_free.restype = None
@@ -122,7 +126,8 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_last_timing", "brx_synchronize", "brx_stream_new", "brx_stream_read", "brx_stream_free",
                     "brx_host_alloc", "brx_host_free", "brx_stream_new_bounded", "brx_generate_batch", "brx_compact_batch",
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
-                    "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal"]
+                    "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
+                    "brx_stream_advance", "brx_stream_ready"]
 
 
 def status_str(code: int) -> str:
@@ -131,7 +136,8 @@ def status_str(code: int) -> str:
 
 # brx_ctx_set_option (include/brx.h, BRX_OPTION_*): explicit knobs -- neither the library nor this module reads the environment
 OPTIONS = {"command_loop": 1, "loop_build": 2, "queue_order": 3, "hand_up": 4, "levels": 5, "tiny_bytes": 6,
-           "host_in_place": 7, "grid_cap": 8, "small_bytes": 9, "small_waves": 10, "trace": 11, "reader_window": 12, "level4": 13, "reader_mb_room": 14}
+           "host_in_place": 7, "grid_cap": 8, "small_bytes": 9, "small_waves": 10, "trace": 11, "reader_window": 12, "level4": 13, "reader_mb_room": 14,
+           "reader_batch": 15}
 
 
 class Context:
@@ -310,6 +316,31 @@ class Context:
         """Slices of bounded / pulled streams of this context run again with a larger output buffer (one command beyond the slack)."""
         return int(self._lib.brx_last_timing(self._h, 9))
 
+    def reader_slice_launches(self):
+        """Slice launches of bounded / pulled streams on this context since it was made (brx_last_timing 16)."""
+        return int(self._lib.brx_last_timing(self._h, 16))
+
+    def reader_slices(self):
+        """Slices of bounded / pulled streams in those launches (brx_last_timing 17): / reader_slice_launches() = slices per round."""
+        return int(self._lib.brx_last_timing(self._h, 17))
+
+    def advance(self, decompressors):
+        """brx_stream_advance: every streaming Decompressor (or raw brx_stream handle) of this context that is unfinished and has no
+        decoded bytes left to read moves on by one slice, all of them in shared launches.  -> how many moved on."""
+        handles = []
+        for d in decompressors:
+            if isinstance(d, Decompressor):
+                d.prepare()
+                if d._ctx is not self:
+                    raise BrxError("advance: a Decompressor of another context")
+                d = d._stream
+            handles.append(d)
+        arr = (ctypes.c_void_p * len(handles))(*handles)
+        rc = self._lib.brx_stream_advance(arr, len(handles))
+        if rc < 0:
+            raise BrxError("brx_stream_advance failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+        return rc
+
     def last_lean_listed(self):
         """Streams of the most recent launch that the lean instance (short streams, 32 waves per CU) left to the regular kernel:
         the ones larger than its limit plus the short ones it gave up on (errors, block switches, large tables)."""
@@ -462,6 +493,16 @@ _PINNED = {}
 _default_ctx = None
 
 
+def advance(streams):
+    """Context.advance over the context of the streams (streaming Decompressors, all on one context)."""
+    streams = list(streams)
+    if not streams:
+        return 0
+    for d in streams:
+        d.prepare()
+    return streams[0]._ctx.advance(streams)
+
+
 def default_context():
     global _default_ctx
     if _default_ctx is None:
@@ -525,6 +566,11 @@ class Decompressor(io.RawIOBase):
             if not self._stream:
                 raise BrxError("brx_stream_new failed")
         return self
+
+    def ready(self):
+        """Decoded bytes a read hands out without decoding anything (brx_stream_ready; between advance() calls)."""
+        self.prepare()
+        return int(self._lib.brx_stream_ready(self._stream))
 
     def readinto(self, b):
         self.prepare()

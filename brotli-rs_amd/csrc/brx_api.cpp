@@ -80,7 +80,7 @@ struct brx_ctx {
     uint8_t *d_lut = nullptr;
     BrxTransform *d_xforms = nullptr;
     uint32_t *d_iac = nullptr;
-    uint32_t *d_counters = nullptr; // BRX_COUNTER_RING x 128 B
+    uint32_t *d_counters = nullptr; // BRX_COUNTER_RING x 128 B, then one more line: the reader rounds' own (one round at a time)
     uint64_t launch_seq = 0;
     // streams whose tables spill the regular kernel's LDS are listed here by it and decoded by the wide kernel launched
     // right behind (BrxKernelArgs::defer): BRX_COUNTER_RING lists of defer_cap stream indices, one per launch in flight
@@ -157,6 +157,21 @@ struct brx_ctx {
     uint32_t fa_readers = 0;                     // owners that still have to copy their stream out of fa_out (under qmu): the next batch
     std::condition_variable fa_cv;               // waits for them before it touches the arena
     uint64_t facade_batches = 0, facade_streams = 0; // batches decode_pending_locked launched / streams in them (brx_last_timing 14 / 15)
+    // Reader rounds (round 7): the slices that bounded / pulled streams ask for go out together, ONE resumable launch over per-stream
+    // descriptors (BrxReaderDesc) for everything queued.  `rq` and the round's members are under rmu (order: mu before rmu); one thread at
+    // a time leads a round (round_busy) and holds `mu` only to enqueue it and to settle its results, not while the GPU runs it.
+    bool reader_batch = true;                     // BRX_OPTION_READER_BATCH: 0 = one stream per launch (the A/B switch)
+    std::mutex rmu;
+    std::vector<brx_stream *> rq;                 // slices asked for, in order of arrival
+    bool round_busy = false;
+    std::condition_variable round_cv;             // a round ended (brx_stream_free of a stream in it waits for that)
+    hipStream_t s_round = nullptr;                // the rounds' own HIP stream: prepares on `stream` go on while a round runs
+    hipEvent_t ev_prep = nullptr;
+    BrxReaderDesc *h_rdesc = nullptr, *d_rdesc = nullptr; // max_grid descriptors: pinned host table, device table
+    uint64_t reader_launches = 0, reader_slices = 0; // slice launches of bounded / pulled streams / slices in them (brx_last_timing 16 / 17)
+    std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
+    std::vector<uint8_t *> stage_free;
+    size_t stage_bytes = 0;
 };
 
 extern "C" const char *brx_last_error(void) { return g_err.c_str(); }
@@ -209,6 +224,7 @@ static void ctx_release(brx_ctx *c) {
         if (q) (void)hipStreamSynchronize(q);
     for (auto &q : c->s_wide)
         if (q) (void)hipStreamSynchronize(q);
+    if (c->s_round) (void)hipStreamSynchronize(c->s_round);
     if (c->ev_last && c->any_launch) (void)hipEventSynchronize(c->ev_last);
     (void)hipFree(c->d_dict);
     (void)hipFree(c->d_lut);
@@ -225,6 +241,11 @@ static void ctx_release(brx_ctx *c) {
     (void)hipFree(c->pool.bitmap);
     (void)hipFree(c->pool.slabs);
     (void)hipFree(c->st_in);
+    (void)hipFree(c->d_rdesc);
+    if (c->h_rdesc) (void)hipHostFree(c->h_rdesc);
+    for (uint8_t *p : c->stage_free) (void)hipHostFree(p);
+    if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
+    if (c->s_round) (void)hipStreamDestroy(c->s_round);
     if (c->fa_in) (void)hipHostFree(c->fa_in);
     if (c->fa_out) (void)hipHostFree(c->fa_out);
     (void)hipFree(c->st_out);
@@ -283,11 +304,11 @@ static int ctx_init(brx_ctx *c, int device) {
     HIP_TRY(hipMalloc(&c->d_dict, sizeof BRX_DICT));
     HIP_TRY(hipMalloc(&c->d_lut, sizeof BRX_CONTEXT_LUT));
     HIP_TRY(hipMalloc(&c->d_xforms, 121 * sizeof(BrxTransform)));
-    HIP_TRY(hipMalloc(&c->d_counters, BRX_COUNTER_RING * 128u));
+    HIP_TRY(hipMalloc(&c->d_counters, (BRX_COUNTER_RING + 1u) * 128u));
     HIP_TRY(hipHostMalloc((void **)&c->h_handed, 16 + 64 * BRX_COUNTER_RING, hipHostMallocMapped)); // (word 0: handed_seq; from word 4: 16 words per launch slot, plan B's counts)
     *c->h_handed = 0u;
     HIP_TRY(hipHostGetDevicePointer((void **)&c->d_handed, c->h_handed, 0));
-    HIP_TRY(hipMemset(c->d_counters, 0, BRX_COUNTER_RING * 128u));
+    HIP_TRY(hipMemset(c->d_counters, 0, (BRX_COUNTER_RING + 1u) * 128u));
     HIP_TRY(hipMalloc(&c->d_pool, sizeof(BrxSlabPool)));
     HIP_TRY(hipMemset(c->d_pool, 0, sizeof(BrxSlabPool)));
     HIP_TRY(hipMemcpy(c->d_dict, BRX_DICT, sizeof BRX_DICT, hipMemcpyHostToDevice));
@@ -401,6 +422,10 @@ extern "C" int brx_ctx_set_option(brx_ctx *c, uint32_t option, int64_t value) {
     case BRX_OPTION_TRACE: c->trace_on = value != 0; break;
     case BRX_OPTION_LEVEL4: c->level4 = value != 0; break;
     case BRX_OPTION_READER_MB_ROOM: c->reader_mb_room = value != 0; break;
+    case BRX_OPTION_READER_BATCH:
+        if (value != 0 && value != 1) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: reader batch is 0 or 1");
+        c->reader_batch = value != 0;
+        break;
     case BRX_OPTION_READER_WINDOW:
         if (value < (1 << 20) || value > (256 << 20)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: reader window is 1 MiB .. 256 MiB");
         c->reader_window = ((size_t)value + 65535u) & ~(size_t)65535;
@@ -544,8 +569,11 @@ static int ensure_order(brx_ctx *c, uint32_t n) {
 static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n,
                   uint8_t *d_out, const uint64_t *d_out_off, uint64_t *d_out_len, int32_t *d_status,
                   const uint32_t *d_order = nullptr, BrxResume *d_resume = nullptr, const BrxSlabPool *d_own_pool = nullptr,
-                  uint8_t *d_out_mirror = nullptr, bool may_plan_b = false, uint32_t n_large = 0xffffffffu) {
+                  uint8_t *d_out_mirror = nullptr, bool may_plan_b = false, uint32_t n_large = 0xffffffffu,
+                  BrxReaderDesc *d_desc = nullptr) {
     BrxKernelArgs a;
+    const bool resumable = d_resume != nullptr || d_desc != nullptr; // (d_desc: a reader round, every stream in buffers of its own)
+    a.rdesc = d_desc;
     a.out_mirror = d_out_mirror;
     a.order = d_order;
     a.in = d_in;
@@ -561,9 +589,9 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
     a.pool = d_own_pool;
     // (what this launch runs at a time: its regular grid; under plan B the wider grids next to it -- together never more than its
     // streams, nor than the chip holds; the grid-cap knob caps each of the four grids)
-    const bool can_plan_b = may_plan_b && !c->no_defer && !c->no_plan_b && d_resume == nullptr && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS;
-    const unsigned slab_waves = d_own_pool ? 0u : (c->grid_cap != 0u && can_plan_b) ? std::min(n, 4u * c->grid_cap) : grid;
-    if (!d_own_pool) {
+    const bool can_plan_b = may_plan_b && !c->no_defer && !c->no_plan_b && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS;
+    const unsigned slab_waves = (d_own_pool || d_desc) ? 0u : (c->grid_cap != 0u && can_plan_b) ? std::min(n, 4u * c->grid_cap) : grid;
+    if (!d_own_pool && !d_desc) { // (a round's streams have their own pools: BrxReaderDesc::pool)
         int rc = ensure_pool(c, pool_need(c, slab_waves));
         if (rc) return rc;
         a.pool = c->d_pool;
@@ -573,7 +601,9 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
     // room and the build with the shorter dependent chain wins; fuller CUs take the one that spares the scalar ALU
     a.loop_build = c->loop_build >= 0 ? (uint32_t)c->loop_build : (grid <= c->max_grid / 16u * BRX_SW_WAVES_PER_CU ? 1u : 0u);
     const size_t ring_slot = (size_t)(c->launch_seq++ % BRX_COUNTER_RING);
-    a.work_counter = c->d_counters + ring_slot * 32u; // one 128-B line per launch
+    // one 128-B line per launch; a reader round -- hundreds of ms on a HIP stream of its own while batches go on -- has a line of its own
+    // that no later launch can take over (rounds run one at a time)
+    a.work_counter = c->d_counters + (d_desc ? (size_t)BRX_COUNTER_RING : ring_slot) * 32u;
     // streams whose tables spill a kernel's LDS table memory are listed for the level that holds them (not in the resumable and
     // bring-up modes): BrxKernelArgs::defer
     a.tiny_bytes = c->tiny_bytes;
@@ -594,7 +624,7 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
     a.start_flag = nullptr;
     a.sw_threshold = c->loop_build >= 0 ? 0u : c->max_grid / 16u * BRX_SW_WAVES_PER_CU;
     uint32_t *regions = nullptr; // this launch's BRX_LIST_REGIONS regions of defer_cap words
-    if (!c->no_defer && d_resume == nullptr && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS) {
+    if (!c->no_defer && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS) {
         int rc = ensure_defer(c, n);
         if (rc) return rc;
         regions = c->d_defer + ring_slot * BRX_LIST_REGIONS * c->defer_cap;
@@ -617,7 +647,7 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
     a.classify = 0u;
     a.n_total = n;
     bool lean = false, lean_tail = false;
-    if (c->small_bytes != 0u && d_resume == nullptr && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS && (d_order == nullptr || n_large < n || n_large == 0xffffffffu)) {
+    if (c->small_bytes != 0u && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS && (d_order == nullptr || n_large < n || n_large == 0xffffffffu)) {
         int rc = ensure_defer(c, n);
         if (rc) return rc;
         a.s_list = c->d_defer + (ring_slot * BRX_LIST_REGIONS + 4u) * c->defer_cap;
@@ -632,7 +662,7 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
     }
     a.debug = nullptr;
     a.trace = nullptr;
-    if (c->trace_on) { // diagnostics: one record per stream
+    if (c->trace_on && !d_desc) { // diagnostics: one record per stream (of batches and single slices; a reader round records none)
         if (c->trace_cap < n) {
             HIP_TRY(hipDeviceSynchronize());
             (void)hipFree(c->d_trace);
@@ -786,12 +816,14 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
         }
     }
     if (timing) HIP_TRY(hipEventRecord(c->ev[3], st));
-    HIP_TRY(hipEventRecord(c->ev_last, st));
+    // (a reader round is not "the most recent launch" of brx_last_timing / brx_last_trace: it leaves that state alone -- it uses no slab
+    // of the context's pool, its counter line is its own, it records no trace)
+    if (!d_desc) HIP_TRY(hipEventRecord(c->ev_last, st));
     if (slab_waves != 0u) {
         HIP_TRY(hipEventRecord(c->ev_done[ring_slot], st));
         c->inflight_waves[ring_slot] = slab_waves;
     }
-    c->last_counter = (a.defer != nullptr || lean) ? a.work_counter : nullptr;
+    if (!d_desc) c->last_counter = (a.defer != nullptr || lean) ? a.work_counter : nullptr;
     c->any_launch = true;
 #ifdef BRX_BRINGUP
     if (a.dump) { // bring-up: parked decoder states for tools/asm_emu.py
@@ -1008,6 +1040,8 @@ extern "C" double brx_last_timing(brx_ctx *c, int which) {
     }
     if (which == 14) return (double)c->facade_batches; // the Read facade: batches launched for queued streams ...
     if (which == 15) return (double)c->facade_streams; // ... and the streams in them (status-25 retries count again)
+    if (which == 16) return (double)c->reader_launches; // slice launches of bounded / pulled streams ...
+    if (which == 17) return (double)c->reader_slices;   // ... and the slices in them
     if (which == 9) return (double)c->stream_regrown; // bounded streams of this context: pauses in front of one item that needed more room behind the window
     if (which == 8) return (double)c->stream_short_slices; // bounded streams of this context: slices that paused in front of an item the resident input did not hold
     if ((which >= 2 && which <= 7) || which == 10 || which == 11) { // counters of the most recent launch (waits for it): 2..4 = streams decoded at level >= which - 1
@@ -1223,6 +1257,22 @@ struct brx_stream {
     uint32_t *d_bitmap = nullptr, *d_slab = nullptr;
     uint64_t *d_meta = nullptr; // in_off[2] | out_off[2] | out_len[1] | status
     uint64_t shift = 0, pos = 0, delivered = 0;
+    bool probe_due = false;     // it ended well before its source did: its owner asks the source for one more byte (bounded_probe)
+    // the slice bounded_prepare has made ready: output position, pause position, end of the window's buffer, input pause
+    uint64_t sl_pos0 = 0, sl_pause_at = 0, sl_cap = 0, sl_in_low = 0;
+    // reader rounds (brx_ctx::rq): 0 = no slice asked for, 1 = queued, 2 = in the running round (under brx_ctx::rmu); who waits for it
+    uint32_t r_state = 0;
+    struct RoundWait *r_wait = nullptr;
+    int r_rc = BRX_SUCCESS;
+    bool in_advance = false;     // (brx_stream_advance: listed once)
+    // the bytes of its last round-decoded slice in pinned host memory: [staged_from, staged_to) -- served with no HIP call, no lock
+    uint8_t *h_stage = nullptr;
+    uint64_t staged_from = 0, staged_to = 0;
+};
+// Whoever waits for slices of a round: a reader (one) or a brx_stream_advance call (many).  Under brx_ctx::rmu.
+struct RoundWait {
+    size_t left = 0;
+    std::condition_variable cv;
 };
 #define BRX_BOUNDED_WINDOW (16u << 20) // the largest Brotli window, (1 << 24) - 16, rounded up
 #define BRX_BOUNDED_CHUNK (4u << 20)   // output decoded per slice
@@ -1241,8 +1291,36 @@ struct brx_stream {
 #define BRX_IN_WINDOW_MAX ((size_t)256u << 20) // the input window grows up to this when one item needs more than it holds
 #define BRX_BOUNDED_BUF_MAX ((size_t)BRX_BOUNDED_BUFSIZE + ((size_t)48u << 20)) // ... the output buffer when one command produces more than the slack
                                       // (an insert or a copy is < 2^24 + 2^22 bytes each, an uncompressed meta-block <= 2^24)
+#define BRX_READER_STAGE ((size_t)BRX_BOUNDED_CHUNK + BRX_BOUNDED_SLACK) // pinned staging per stream of a reader round: a slice + the slack
+#define BRX_READER_STAGE_MAX ((size_t)1 << 30) // ... at most this much per context (streams beyond read from the device, as with option 0)
+
+static void stage_put(brx_ctx *c, brx_stream *s) {
+    if (!s->h_stage) return;
+    if (c) {
+        std::lock_guard<std::mutex> sl(c->stage_mu);
+        c->stage_free.push_back(s->h_stage);
+    } else {
+        (void)hipHostFree(s->h_stage);
+    }
+    s->h_stage = nullptr;
+    s->staged_from = s->staged_to = 0;
+}
+
+static bool stage_get(brx_ctx *c, brx_stream *s) {
+    if (s->h_stage) return true;
+    std::lock_guard<std::mutex> sl(c->stage_mu);
+    if (!c->stage_free.empty()) {
+        s->h_stage = c->stage_free.back();
+        c->stage_free.pop_back();
+    } else if (c->stage_bytes + BRX_READER_STAGE <= BRX_READER_STAGE_MAX) {
+        s->h_stage = (uint8_t *)brx_host_alloc(BRX_READER_STAGE);
+        if (s->h_stage) c->stage_bytes += BRX_READER_STAGE;
+    }
+    return s->h_stage != nullptr;
+}
 
 static void bounded_release(brx_stream *s) {
+    stage_put(s->ctx, s);
     if (!s->d_buf && !s->d_inwin) return;
     if (s->ctx) (void)hipSetDevice(s->ctx->device);
     (void)hipFree(s->d_inwin);
@@ -1385,9 +1463,15 @@ static int bounded_grow_out(brx_stream *s, uint64_t need_abs) {
     return BRX_SUCCESS;
 }
 
-// Decode the next slice: up to BRX_BOUNDED_CHUNK more bytes (to the next command boundary past it).
-static int bounded_step(brx_stream *s, std::unique_lock<std::mutex> &lk) {
+// The next slice -- up to BRX_BOUNDED_CHUNK more bytes (to the next command boundary past it) -- in three parts: bounded_prepare (the
+// stream's owner: slide, grow, refill through its pull callback), the launch (bounded_slice_one: this stream alone; round_launch: every
+// queued stream at once), bounded_finish (what the slice's result means for the stream; the leader of a round runs it for all of them).
+static int bounded_prepare(brx_stream *s, std::unique_lock<std::mutex> &lk) {
     brx_ctx *c = s->ctx;
+    // (a slice is prepared once every decoded byte has been read: the staging of the last one is spent.  Only a round stages the next
+    // one -- a slice of its own, BRX_OPTION_READER_BATCH = 0, is read from the device -- and the staged copy runs past the slice's end,
+    // over bytes not decoded yet: a range left over from an earlier round must not serve them)
+    s->staged_from = s->staged_to = 0;
     HIP_TRY(hipSetDevice(c->device));
     if (s->pos - s->shift >= (uint64_t)BRX_BOUNDED_WINDOW + BRX_BOUNDED_SLIDE_MIN) {
         // slide the window: keep the last BRX_BOUNDED_WINDOW bytes (every back-reference reaches at most that far); the
@@ -1432,61 +1516,230 @@ static int bounded_step(brx_stream *s, std::unique_lock<std::mutex> &lk) {
         }
     }
     s->no_progress = false;
-    const uint64_t cap_abs = std::min<uint64_t>(s->shift + s->buf_size, BRX_STREAM_LIMIT);
-    const uint64_t pause_at = s->pos + BRX_BOUNDED_CHUNK;
-    uint8_t *virt = (uint8_t *)((uintptr_t)s->d_buf - (uintptr_t)s->shift); // address of output byte 0, were it still resident
-    {
-        uint64_t meta[4] = {0, s->in_fill, 0, cap_abs};
-        HIP_TRY(hipMemcpyAsync(s->d_meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
-        // While the source has more, the slice pauses a margin (1/32 of the window: 256 KiB) short of the resident end -- at a
-        // command or meta-block boundary, or in the middle of a literal run -- and a segment that still runs into that end (a
-        // header, an uncompressed block, one whole command of the C++ loop) is taken back by the kernel itself: the slice
-        // pauses in FRONT of it (brx_kernels.hip, resumable mode).  So UnexpectedEOF comes out of a slice only when it was told
-        // that the resident input is all there is: the source is dry -- or `stalled`: the last slice paused where it had started, the
-        // window could not be moved or filled any further and could not grow either (one item that needs more than 256 MiB of input
-        // resident); this slice reports what it finds.  (UnexpectedEOF that the reference raises for a FORMAT error -- a bad
-        // MSKIPLEN, Q10 -- is not taken back by the kernel: ST_EOF_FORMAT in brx_kernels.hip.)
-        const size_t margin = s->in_window / BRX_IN_MARGIN_DIV;
-        const uint64_t in_low = s->src_eof || s->in_fill <= margin || s->stalled ? ~0ull : 8ull * (s->in_fill - margin);
-        const uint64_t pz[4] = {pause_at, s->in_slide_pending, in_low, s->no_mb_room ? 1ull : 0ull}; // (need_room on the way in: 1 = no pause in front of whole meta-blocks)
-        HIP_TRY(hipMemcpyAsync((uint8_t *)s->d_rec + offsetof(BrxResume, pause_at), pz, 32, hipMemcpyHostToDevice, c->stream));
-        int rc = launch(c, c->stream, false, s->d_inwin, s->d_meta, 1, virt, s->d_meta + 2, s->d_meta + 4,
-                        (int32_t *)(s->d_meta + 5), nullptr, s->d_rec, s->d_pool);
-        if (rc) return rc;
-        uint64_t res[2] = {0, 0}, cur = 0, need_room = 0;
-        HIP_TRY(hipMemcpyAsync(&need_room, &s->d_rec->need_room, 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(res, s->d_meta + 4, 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(&cur, &s->d_rec->lds[BRX_RESUME_CURSOR_WORD], 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        const int32_t st = (int32_t)(res[1] & 0xffffffffu);
-        if (st == BRX_OUTPUT_TOO_SMALL) return BRX_ERR_OUT_OF_MEMORY; // (not reached since round 5: the kernel takes such an item back and
-                                                                      // pauses in front of it -- need_room below; kept as the caller's fallback)
-        s->in_slide_pending = 0;
-        s->stalled = false;
-        s->pos = res[0];
-        if (st != BRX_PAUSED) {
-            s->finished = true;
-            s->status = st;
-            if (st == BRX_OK && !s->src_eof) { // bytes behind the end of the stream (StreamEnd, src/lib.rs:2155-2167)?
-                uint8_t probe;
-                if (stream_pull(s, &probe, 1, lk) != 0) s->status = BRX_EXPECTED_END_OF_STREAM;
-                else s->src_eof = true;
-            }
-        } else {
-            const size_t cursor = (size_t)(cur >> 3);
-            // One item (a long copy or insert, an uncompressed meta-block) runs to `need_room` and did not fit behind the window: the
-            // kernel took it back and paused in front of it.  The next slice first slides the window; if the item still does not
-            // fit, the buffer grows to hold it (bounded_grow_out) -- nothing is decoded twice, nothing is put back.
-            s->want_room_optional = (need_room >> 63) != 0;
-            need_room &= ~(1ull << 63);
-            s->want_room = need_room;
-            if (need_room) c->stream_regrown++;
-            s->no_progress = cursor == s->in_cursor && res[0] == pos0 && need_room == 0;
-            if (res[0] < pause_at && cur < in_low) c->stream_short_slices++; // (paused in front of something that did not fit what was resident)
-            s->in_cursor = cursor;
-        }
-        return BRX_SUCCESS;
+    s->sl_pos0 = pos0;
+    s->sl_cap = std::min<uint64_t>(s->shift + s->buf_size, BRX_STREAM_LIMIT);
+    s->sl_pause_at = s->pos + BRX_BOUNDED_CHUNK;
+    // While the source has more, the slice pauses a margin (1/32 of the window: 256 KiB) short of the resident end -- at a
+    // command or meta-block boundary, or in the middle of a literal run -- and a segment that still runs into that end (a
+    // header, an uncompressed block, one whole command of the C++ loop) is taken back by the kernel itself: the slice
+    // pauses in FRONT of it (brx_kernels.hip, resumable mode).  So UnexpectedEOF comes out of a slice only when it was told
+    // that the resident input is all there is: the source is dry -- or `stalled`: the last slice paused where it had started, the
+    // window could not be moved or filled any further and could not grow either (one item that needs more than 256 MiB of input
+    // resident); this slice reports what it finds.  (UnexpectedEOF that the reference raises for a FORMAT error -- a bad
+    // MSKIPLEN, Q10 -- is not taken back by the kernel: ST_EOF_FORMAT in brx_kernels.hip.)
+    const size_t margin = s->in_window / BRX_IN_MARGIN_DIV;
+    s->sl_in_low = s->src_eof || s->in_fill <= margin || s->stalled ? ~0ull : 8ull * (s->in_fill - margin);
+    return BRX_SUCCESS;
+}
+
+static int bounded_finish(brx_stream *s, uint64_t out_len, int32_t st, uint64_t need_room, uint64_t cur) {
+    brx_ctx *c = s->ctx;
+    if (st == BRX_OUTPUT_TOO_SMALL) return BRX_ERR_OUT_OF_MEMORY; // (not reached since round 5: the kernel takes such an item back and
+                                                                  // pauses in front of it -- need_room below; kept as the caller's fallback)
+    s->in_slide_pending = 0;
+    s->stalled = false;
+    s->pos = out_len;
+    if (st != BRX_PAUSED) {
+        s->finished = true;
+        s->status = st;
+        s->probe_due = st == BRX_OK && !s->src_eof; // bytes behind the end of the stream (StreamEnd, src/lib.rs:2155-2167)?  Its owner asks
+    } else {
+        const size_t cursor = (size_t)(cur >> 3);
+        // One item (a long copy or insert, an uncompressed meta-block) runs to `need_room` and did not fit behind the window: the
+        // kernel took it back and paused in front of it.  The next slice first slides the window; if the item still does not
+        // fit, the buffer grows to hold it (bounded_grow_out) -- nothing is decoded twice, nothing is put back.
+        s->want_room_optional = (need_room >> 63) != 0;
+        need_room &= ~(1ull << 63);
+        s->want_room = need_room;
+        if (need_room) c->stream_regrown++;
+        s->no_progress = cursor == s->in_cursor && out_len == s->sl_pos0 && need_room == 0;
+        if (out_len < s->sl_pause_at && cur < s->sl_in_low) c->stream_short_slices++; // (paused in front of something that did not fit what was resident)
+        s->in_cursor = cursor;
     }
+    return BRX_SUCCESS;
+}
+
+// (the owner, once its stream has ended well: one byte more from the source makes it ExpectedEndOfStream)
+static void bounded_probe(brx_stream *s, std::unique_lock<std::mutex> &lk) {
+    if (!s->probe_due) return;
+    s->probe_due = false;
+    uint8_t probe;
+    if (stream_pull(s, &probe, 1, lk) != 0) s->status = BRX_EXPECTED_END_OF_STREAM;
+    else s->src_eof = true;
+}
+
+// The prepared slice of ONE stream in a launch of its own (BRX_OPTION_READER_BATCH = 0; the way every slice ran before round 7).
+static int bounded_slice_one(brx_stream *s) {
+    brx_ctx *c = s->ctx;
+    uint8_t *virt = (uint8_t *)((uintptr_t)s->d_buf - (uintptr_t)s->shift); // address of output byte 0, were it still resident
+    uint64_t meta[4] = {0, s->in_fill, 0, s->sl_cap};
+    HIP_TRY(hipMemcpyAsync(s->d_meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
+    const uint64_t pz[4] = {s->sl_pause_at, s->in_slide_pending, s->sl_in_low, s->no_mb_room ? 1ull : 0ull}; // (need_room on the way in: 1 = no pause in front of whole meta-blocks)
+    HIP_TRY(hipMemcpyAsync((uint8_t *)s->d_rec + offsetof(BrxResume, pause_at), pz, 32, hipMemcpyHostToDevice, c->stream));
+    int rc = launch(c, c->stream, false, s->d_inwin, s->d_meta, 1, virt, s->d_meta + 2, s->d_meta + 4,
+                    (int32_t *)(s->d_meta + 5), nullptr, s->d_rec, s->d_pool);
+    if (rc) return rc;
+    c->reader_launches++;
+    c->reader_slices++;
+    uint64_t res[2] = {0, 0}, cur = 0, need_room = 0;
+    HIP_TRY(hipMemcpyAsync(&need_room, &s->d_rec->need_room, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(res, s->d_meta + 4, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&cur, &s->d_rec->lds[BRX_RESUME_CURSOR_WORD], 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return bounded_finish(s, res[0], (int32_t)(res[1] & 0xffffffffu), need_room, cur);
+}
+
+// What a slice's outcome `rc` does to the stream (under the context's lock; the leader of a round runs it for the round's streams).
+static void slice_settle(brx_ctx *c, brx_stream *s, int rc) {
+    if (rc == BRX_SUCCESS) return;
+    bounded_release(s);
+    if (rc == BRX_ERR_OUT_OF_MEMORY && !s->finished && s->read_fn != nullptr) {
+        // (over a reader the compressed bytes behind the window are gone: no second way)
+        s->lib_rc = fail(BRX_ERR_OUT_OF_MEMORY, "brx_stream_read: one item of the stream needs more device memory than the bounded reader may take (or an allocation failed); decode this stream from memory (brx_stream_new)");
+    } else if (rc == BRX_ERR_OUT_OF_MEMORY && !s->finished) {
+        // a single command (a copy or an uncompressed meta-block) larger than the slack: the whole stream is decoded the unbounded
+        // way, and its reader goes on from where it stands.  It is queued like any whole stream and goes out with the facade's next
+        // batch, under that batch's leader protocol (its owner leads or waits in brx_stream_read).
+        s->bounded = false;
+        s->served = (size_t)s->delivered;
+        std::lock_guard<std::mutex> ql(c->qmu);
+        c->pending.push_back(s);
+        if (c->facade_busy) c->new_cv.notify_one();
+    } else {
+        s->lib_rc = rc;
+    }
+}
+
+// One reader round: the prepared slices of `b` (at most max_grid streams, each in the `2` state) in ONE launch.  Enqueued under the
+// context's lock -- one descriptor upload, the launch, one download of the results, one copy per stream of its slice into its pinned
+// staging -- and waited for WITHOUT it (owners prepare their next slices meanwhile); then every stream's result is settled.
+static int round_launch(brx_ctx *c, const std::vector<brx_stream *> &b) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->s_round) {
+        HIP_TRY(hipStreamCreateWithFlags(&c->s_round, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
+    }
+    if (!c->h_rdesc) {
+        HIP_TRY(hipHostMalloc((void **)&c->h_rdesc, (size_t)c->max_grid * sizeof(BrxReaderDesc), hipHostMallocDefault));
+        hipError_t e = hipMalloc(&c->d_rdesc, (size_t)c->max_grid * sizeof(BrxReaderDesc));
+        if (e != hipSuccess) {
+            (void)hipHostFree(c->h_rdesc);
+            c->h_rdesc = nullptr;
+            c->d_rdesc = nullptr;
+            return fail(BRX_ERR_OUT_OF_MEMORY, "reader descriptor allocation failed", e);
+        }
+    }
+    const uint32_t n = (uint32_t)b.size();
+    for (uint32_t i = 0; i < n; i++) {
+        const brx_stream *s = b[i];
+        BrxReaderDesc &d = c->h_rdesc[i];
+        memset(&d, 0, sizeof d);
+        d.in = s->d_inwin;
+        d.in_len = s->in_fill;
+        d.out = (uint8_t *)((uintptr_t)s->d_buf - (uintptr_t)s->shift);
+        d.cap = s->sl_cap;
+        d.rec = s->d_rec;
+        d.pool = s->d_pool;
+        d.pause_at = s->sl_pause_at;
+        d.in_slide = s->in_slide_pending;
+        d.in_low = s->sl_in_low;
+        d.room_in = s->no_mb_room ? 1ull : 0ull;
+    }
+    HIP_TRY(hipEventRecord(c->ev_prep, c->stream)); // (the owners' slides and refills of these streams went to the context's stream)
+    HIP_TRY(hipStreamWaitEvent(c->s_round, c->ev_prep, 0));
+    HIP_TRY(hipMemcpyAsync(c->d_rdesc, c->h_rdesc, (size_t)n * sizeof(BrxReaderDesc), hipMemcpyHostToDevice, c->s_round));
+    int rc = launch(c, c->s_round, false, nullptr, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                    false, 0xffffffffu, c->d_rdesc);
+    if (rc) return rc;
+    c->reader_launches++;
+    c->reader_slices += n;
+    HIP_TRY(hipMemcpyAsync(c->h_rdesc, c->d_rdesc, (size_t)n * sizeof(BrxReaderDesc), hipMemcpyDeviceToHost, c->s_round));
+    // The slice's bytes, in the round's stream order: from its first position to its pause position + the slack (a slice ends at the
+    // first command boundary behind its pause position; what a longer one made -- a whole meta-block of several MiB run by the fast
+    // loop -- is read from the device like before).  Never past the window's buffer.
+    for (uint32_t i = 0; i < n; i++) {
+        brx_stream *s = b[i];
+        s->staged_from = s->staged_to = 0;
+        if (!stage_get(c, s)) continue;
+        const uint64_t end = std::min<uint64_t>(s->sl_cap, s->sl_pause_at + BRX_BOUNDED_SLACK);
+        const size_t len = end > s->sl_pos0 ? (size_t)std::min<uint64_t>(end - s->sl_pos0, BRX_READER_STAGE) : 0u;
+        if (len) HIP_TRY(hipMemcpyAsync(s->h_stage, s->d_buf + (s->sl_pos0 - s->shift), len, hipMemcpyDeviceToHost, c->s_round));
+        s->staged_to = len; // (relative until the round is done)
+    }
+    return BRX_SUCCESS;
+}
+
+static void round_run(brx_ctx *c, const std::vector<brx_stream *> &b) {
+    std::unique_lock<std::mutex> lk(c->mu);
+    int rc = round_launch(c, b);
+    lk.unlock();
+    if (rc == BRX_SUCCESS) {
+        hipError_t e = hipStreamSynchronize(c->s_round); // (the one wait of the round; the context's lock is free meanwhile)
+        if (e != hipSuccess) rc = fail(BRX_ERR_HIP, "reader round: hipStreamSynchronize", e);
+    }
+    lk.lock();
+    for (size_t i = 0; i < b.size(); i++) {
+        brx_stream *s = b[i];
+        int r = rc;
+        if (r == BRX_SUCCESS) {
+            const BrxReaderDesc &d = c->h_rdesc[i];
+            const uint64_t len = s->staged_to;
+            s->staged_from = s->sl_pos0;
+            s->staged_to = s->sl_pos0 + len;
+            r = bounded_finish(s, d.out_len, d.status, d.need_room, d.cursor);
+        } else {
+            s->staged_from = s->staged_to = 0;
+        }
+        slice_settle(c, s, r);
+    }
+}
+
+// Queue the prepared slices of `v` and return once every one of them has run (called with the context's lock held; it is released
+// meanwhile).  The first thread that finds no round running leads one over everything queued; the others wait on their own
+// RoundWait.  A round that ends wakes the waiters it has served and the owner of the oldest request left, who leads the next one.
+// The leader never touches a stream it does not own outside of the round itself: pulls and probes are its owner's.
+static void rounds_wait(brx_ctx *c, const std::vector<brx_stream *> &v, std::unique_lock<std::mutex> &lk) {
+    if (v.empty()) return;
+    RoundWait w;
+    std::unique_lock<std::mutex> rl(c->rmu);
+    for (brx_stream *s : v) {
+        s->r_state = 1u;
+        s->r_wait = &w;
+        c->rq.push_back(s);
+    }
+    w.left = v.size();
+    lk.unlock();
+    while (w.left != 0u) {
+        if (c->round_busy || c->rq.empty()) {
+            w.cv.wait(rl);
+            continue;
+        }
+        c->round_busy = true;
+        const size_t k = std::min<size_t>(c->rq.size(), std::max(c->max_grid, 1u)); // (what the chip runs at a time; the rest: next round)
+        std::vector<brx_stream *> b(c->rq.begin(), c->rq.begin() + (ptrdiff_t)k);
+        c->rq.erase(c->rq.begin(), c->rq.begin() + (ptrdiff_t)k);
+        for (brx_stream *s : b) s->r_state = 2u;
+        rl.unlock();
+        try {
+            round_run(c, b);
+        } catch (...) { // (a host allocation failed: nobody may be left waiting for these streams)
+            for (brx_stream *s : b)
+                if (s->lib_rc == BRX_SUCCESS && !s->finished) s->lib_rc = BRX_ERR_OUT_OF_MEMORY;
+        }
+        rl.lock();
+        c->round_busy = false;
+        for (brx_stream *s : b) { // (the streams are their owners' again from here on: not touched after this loop)
+            RoundWait *o = s->r_wait;
+            s->r_state = 0u;
+            s->r_wait = nullptr;
+            if (--o->left == 0u && o != &w) o->cv.notify_one();
+        }
+        if (!c->rq.empty() && c->rq.front()->r_wait != &w) c->rq.front()->r_wait->cv.notify_one(); // the next round's leader
+        c->round_cv.notify_all();
+    }
+    if (!c->round_busy && !c->rq.empty()) c->rq.front()->r_wait->cv.notify_one(); // (this thread may have been woken to lead)
+    rl.unlock();
+    lk.lock();
 }
 
 static void stream_detach(brx_stream *s) {
@@ -1683,14 +1936,27 @@ extern "C" int64_t brx_stream_read(brx_stream *s, uint8_t *buf, size_t len) {
     BRX_GUARD_BEGIN
     if (!s) return -(int64_t)BRX_UNEXPECTED_EOF;
     if (s->bounded) {
+        if (s->delivered >= s->staged_from && s->delivered < std::min(s->pos, s->staged_to)) {
+            // decoded by a reader round: the bytes are in the stream's pinned staging (no HIP call, not the context's lock)
+            const size_t k = (size_t)std::min<uint64_t>(len, std::min(s->pos, s->staged_to) - s->delivered);
+            if (k) memcpy(buf, s->h_stage + (s->delivered - s->staged_from), k);
+            s->delivered += k;
+            return (int64_t)k;
+        }
         brx_ctx *c = s->ctx;
         if (!c) return -(int64_t)1000 + BRX_ERR_INVALID_ARGUMENT;
         std::unique_lock<std::mutex> lk(c->mu);
-        for (;;) {
+        while (s->bounded) {
             if (s->lib_rc != BRX_SUCCESS) return -(int64_t)1000 + s->lib_rc;
             if (s->delivered < s->pos) {
                 const size_t k = (size_t)std::min<uint64_t>(len, s->pos - s->delivered);
                 if (k == 0) return 0;
+                if (s->delivered >= s->staged_from && s->delivered < s->staged_to) { // (staged by a round that ended meanwhile)
+                    const size_t m = (size_t)std::min<uint64_t>(k, s->staged_to - s->delivered);
+                    memcpy(buf, s->h_stage + (s->delivered - s->staged_from), m);
+                    s->delivered += m;
+                    return (int64_t)m;
+                }
                 if (hipSetDevice(c->device) != hipSuccess ||
                     hipMemcpy(buf, s->d_buf + (s->delivered - s->shift), k, hipMemcpyDeviceToHost) != hipSuccess) {
                     s->lib_rc = fail(BRX_ERR_HIP, "brx_stream_read: device to host copy failed");
@@ -1700,6 +1966,7 @@ extern "C" int64_t brx_stream_read(brx_stream *s, uint8_t *buf, size_t len) {
                 return (int64_t)k;
             }
             if (s->finished) {
+                bounded_probe(s, lk);
                 bounded_release(s);
                 return s->status == BRX_OK ? 0 : -(int64_t)s->status; // the bytes before an error were served first
             }
@@ -1707,29 +1974,16 @@ extern "C" int64_t brx_stream_read(brx_stream *s, uint8_t *buf, size_t len) {
                 int rc = bounded_init(s);
                 if (rc) { bounded_release(s); s->lib_rc = rc; continue; }
             }
-            int rc = bounded_step(s, lk);
-            if (rc == BRX_ERR_OUT_OF_MEMORY && !s->finished && s->read_fn != nullptr) {
-                // (over a reader the compressed bytes behind the window are gone: no second way)
-                bounded_release(s);
-                s->lib_rc = fail(BRX_ERR_OUT_OF_MEMORY, "brx_stream_read: one item of the stream needs more device memory than the bounded reader may take (or an allocation failed); decode this stream from memory (brx_stream_new)");
-                continue;
+            int rc = bounded_prepare(s, lk);
+            if (rc == BRX_SUCCESS && s->ctx == nullptr) rc = BRX_ERR_INVALID_ARGUMENT; // (the context went away during a pull)
+            else if (rc == BRX_SUCCESS && !c->reader_batch) rc = bounded_slice_one(s);
+            else if (rc == BRX_SUCCESS) { // a reader round: queued with the slices other threads ask for, one launch for all of them
+                rounds_wait(c, std::vector<brx_stream *>{s}, lk);
+                continue; // (settled by the round's leader)
             }
-            if (rc == BRX_ERR_OUT_OF_MEMORY && !s->finished) {
-                // a single command (a copy or an uncompressed meta-block) larger than the slack: decode the whole stream
-                // the unbounded way and go on serving from where this reader stands
-                bounded_release(s);
-                s->bounded = false;
-                s->served = (size_t)s->delivered;
-                {
-                    std::lock_guard<std::mutex> ql(c->qmu);
-                    c->pending.push_back(s);
-                }
-                decode_pending_locked(c, s);
-                c->qcv.notify_all(); // (streams of other threads went out with it)
-                break;
-            }
-            if (rc) { bounded_release(s); s->lib_rc = rc; }
+            slice_settle(c, s, rc);
         }
+        // (a stream that fell back to whole-stream decoding is queued: its owner leads the facade's next batch or waits for it, below)
     }
     if (!s->decoded.load(std::memory_order_acquire)) {
         // One reader leads: it decodes everything queued on the context -- its own stream and whatever other threads have made since the
@@ -1843,6 +2097,22 @@ extern "C" int64_t brx_stream_read(brx_stream *s, uint8_t *buf, size_t len) {
 
 extern "C" void brx_stream_free(brx_stream *s) {
     if (!s) return;
+    try {
+        if (brx_ctx *c = s->ctx) { // a slice it asked for: taken back while queued, waited for while a round runs it
+            std::unique_lock<std::mutex> rl(c->rmu);
+            if (s->r_state == 1u) {
+                auto &q = c->rq;
+                q.erase(std::remove(q.begin(), q.end(), s), q.end());
+                RoundWait *o = s->r_wait;
+                s->r_state = 0u;
+                s->r_wait = nullptr;
+                if (--o->left == 0u) o->cv.notify_one();
+                if (!c->round_busy && !q.empty()) q.front()->r_wait->cv.notify_one();
+            }
+            while (s->r_state == 2u) c->round_cv.wait(rl);
+        }
+    } catch (...) {
+    }
     bounded_release(s);
     try {
         if (brx_ctx *c = s->ctx) {
@@ -1861,4 +2131,55 @@ extern "C" void brx_stream_free(brx_stream *s) {
     } catch (...) {
     }
     delete s;
+}
+
+extern "C" int brx_stream_advance(brx_stream *const *streams, uint32_t n) {
+    BRX_GUARD_BEGIN
+    if (n == 0u) return 0;
+    if (!streams) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_stream_advance: streams is NULL");
+    brx_ctx *c = streams[0] ? streams[0]->ctx : nullptr;
+    for (uint32_t i = 0; i < n; i++)
+        if (!streams[i] || !streams[i]->ctx || streams[i]->ctx != c)
+            return fail(BRX_ERR_INVALID_ARGUMENT, "brx_stream_advance: a NULL stream, or streams of different contexts");
+    std::unique_lock<std::mutex> lk(c->mu);
+    std::vector<brx_stream *> go;
+    try {
+        for (uint32_t i = 0; i < n; i++) {
+            brx_stream *s = streams[i];
+            if (!s->bounded || s->in_advance || s->lib_rc != BRX_SUCCESS || s->finished || s->delivered < s->pos) continue;
+            s->in_advance = true;
+            go.push_back(s);
+        }
+        for (brx_stream *s : go) s->in_advance = false;
+        size_t k = 0;
+        for (brx_stream *s : go) { // (this thread owns them all: their pulls run here, the lock released around each)
+            if (!s->d_buf) {
+                int rc = bounded_init(s);
+                if (rc) { bounded_release(s); s->lib_rc = rc; continue; }
+            }
+            int rc = bounded_prepare(s, lk);
+            if (rc == BRX_SUCCESS && s->ctx == nullptr) rc = BRX_ERR_INVALID_ARGUMENT;
+            if (rc == BRX_SUCCESS) go[k++] = s;
+            else slice_settle(c, s, rc);
+        }
+        go.resize(k);
+    } catch (...) {
+        for (brx_stream *s : go) s->in_advance = false;
+        throw;
+    }
+    const int launched = (int)go.size();
+    if (!c->reader_batch) {
+        for (brx_stream *s : go) slice_settle(c, s, bounded_slice_one(s));
+    } else {
+        rounds_wait(c, go, lk); // (the streams may be freed by another thread from here on: not touched again)
+    }
+    return launched;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+extern "C" int64_t brx_stream_ready(const brx_stream *s) {
+    if (!s) return 0;
+    if (s->bounded) return (int64_t)(s->pos - s->delivered);
+    if (!s->decoded.load(std::memory_order_acquire) || s->view) return 0;
+    return (int64_t)(s->out.size() - s->served);
 }

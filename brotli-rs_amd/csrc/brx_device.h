@@ -122,6 +122,27 @@ struct BrxResume {
                                             // window's first dword): 2048 B ring + 6912 B tables + 768 B scratch, st[] follows
 #define BRX_PAUSED 28 // per-stream status of a paused resumable decode (never leaves brx_api.cpp)
 
+// A slice round (brx_api.cpp, reader rounds): the slices of many bounded / pulled streams in ONE resumable launch.  Each stream
+// lives in buffers of its own, so stream `sid` of the launch is described here instead of by in / in_off / out / out_off / resume.
+// The host writes the first part, the kernel the second; the table goes up and comes back in one copy each.
+struct BrxReaderDesc {
+    const uint8_t *in;        // the stream's input window, and
+    uint64_t in_len;          // ... the bytes resident in it
+    uint8_t *out;             // address of output byte 0, were it still resident (the window's base - its shift)
+    uint64_t cap;             // absolute output position the window's buffer ends at
+    BrxResume *rec;           // its state record
+    const BrxSlabPool *pool;  // its own one-slab pool (a paused stream keeps its slab across slices)
+    uint64_t pause_at, in_slide, in_low, room_in; // what BrxResume::pause_at / in_slide / in_low / need_room carry into a slice of its own
+    // written by the kernel:
+    uint64_t out_len;         // output position the slice ended at
+    uint64_t need_room;       // as BrxResume::need_room at a pause, else 0
+    uint64_t cursor;          // the parked input cursor (bits from the window's first dword) at a pause
+    int32_t status;           // BRX_PAUSED, or the stream's final status
+    uint32_t pad;
+    uint64_t pad2[2];
+};
+static_assert(sizeof(BrxReaderDesc) == 128, "one 128-B line per stream");
+
 struct BrxKernelArgs {
     const uint8_t *in;
     const uint64_t *in_off;
@@ -182,6 +203,8 @@ struct BrxKernelArgs {
                             // BRX_DUMP_WORDS words: {stream id, command index, 14 spare, the wave's whole LDS}
     uint32_t dump_interval, dump_max;
     BrxResume *resume;      // nullptr, or one record per stream: resumable mode (see BrxResume)
+    BrxReaderDesc *rdesc;   // nullptr, or one descriptor per stream: resumable mode over streams in buffers of their own (regular
+                            // kernel only; in / in_off / out / out_off / out_len / status / resume / pool are then not used)
     uint8_t *out_mirror;    // nullptr, or the device-visible address of pinned host memory laid out like `out`: output bytes are
                             // stored to both (the D2H copy fused into the decode)
     uint32_t launch_seq;    // sequence number of this launch on its context, and

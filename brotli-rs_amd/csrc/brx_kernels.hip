@@ -2423,8 +2423,22 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
         // plan B: the pre-pass has classified every stream of this queue; the ones of the wider levels are theirs
         if (a.cls != nullptr && a.prepass == 0u && rfl((u32)a.cls[sid]) != 0u) continue;
 #endif
-        const u64 i0 = a.in_off[sid], i1 = a.in_off[sid + 1u];
-        const u64 o0 = a.out_off[sid], o1 = a.out_off[sid + 1u];
+        // (a slice round, BrxKernelArgs::rdesc: the stream's own buffers, as offsets 0 .. length into them)
+        const u8 *a_in = a.in;
+        u8 *a_out = a.out;
+        const BrxSlabPool *a_pool = a.pool;
+        u64 i0, i1, o0, o1;
+#if BRX_LEVEL == 0
+        BrxReaderDesc *const rd = a.rdesc != nullptr ? a.rdesc + sid : nullptr;
+        if (rd != nullptr) {
+            a_in = rd->in; a_out = rd->out; a_pool = rd->pool;
+            i0 = 0ull; i1 = rd->in_len; o0 = 0ull; o1 = rd->cap;
+        } else
+#endif
+        {
+            i0 = a.in_off[sid]; i1 = a.in_off[sid + 1u];
+            o0 = a.out_off[sid]; o1 = a.out_off[sid + 1u];
+        }
 #if BRX_LEVEL == 0
         if (two_walk) { // walk 0: sizes >= 2 x mean, 1: [mean, 2 x mean), 2: [mean / 2, mean), 3: the rest
             const u64 len = i1 >= i0 ? i1 - i0 : 0ull;
@@ -2435,14 +2449,14 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
         {
             Dec d;
             d.lane = lane;
-            const u8 *inp = a.in + i0;
+            const u8 *inp = a_in + i0;
             const u32 mis = (u32)((uintptr_t)inp & 3u);
             d.in_words = (const u32 *)(inp - mis);
             const u64 in_len = i1 >= i0 ? i1 - i0 : 0ull; // a decreasing offset table gives an empty stream, never a wild range
             d.w_end = (u32)((mis + in_len + 3u) >> 2);
             d.bitend = 8ull * (mis + in_len);
             d.bitpos = 8ull * mis;
-            d.out = a.out + o0;
+            d.out = a_out + o0;
             d.mirror = a.out_mirror != nullptr ? a.out_mirror + o0 : nullptr;
             const u64 capacity = o1 >= o0 ? o1 - o0 : 0ull;
             d.cap = capacity > 0xffffff00ull ? 0xffffff00u : (u32)capacity;
@@ -2457,7 +2471,7 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
             d.lds_top = 0;
             d.scr_top = 0;
             d.scratch = nullptr;
-            d.pool = a.pool;
+            d.pool = a_pool;
             d.t_dict = a.t.dict;
             d.t_xforms = a.t.xforms;
             d.t_lut = (const u32 *)a.t.context_lut;
@@ -2467,15 +2481,15 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
                 s.st[ST_IACTAB] = (u32)(uintptr_t)a.t.iac; s.st[ST_IACTAB + 1] = (u32)((u64)(uintptr_t)a.t.iac >> 32);
                 s.st[ST_PAUSE_AT] = 0xffffffffu; s.st[ST_PAUSE_AT + 1] = 0xffffffffu;
                 s.st[ST_IN_LOW] = 0xffffffffu; s.st[ST_IN_LOW + 1] = 0xffffffffu;
-                s.st[ST_SPEC] = ((a.resume == nullptr && a.debug_stop == 0u) ? 1u : 0u) | (a.debug_stop == 6u ? 2u : 0u);
+                s.st[ST_SPEC] = ((a.resume == nullptr && a.rdesc == nullptr && a.debug_stop == 0u) ? 1u : 0u) | (a.debug_stop == 6u ? 2u : 0u);
             }
             if (lane < 32u) s.pad[lane] = 0u;
         }
 #if BRX_LEVEL == 0
-        if (a.resume != nullptr) {
+        if (a.resume != nullptr || rd != nullptr) {
             // ---- resumable mode: one stream decoded in slices against a sliding output window (brx_api.cpp, streaming
             // Read facade).  Pauses only between the out-of-line segments, where the whole state sits in LDS.
-            BrxResume *rec = a.resume + sid;
+            BrxResume *rec = rd != nullptr ? rd->rec : a.resume + sid;
             enum { PH_FRAME = 0, PH_LOOP = 1, PH_HEADER = 2, PH_ASMEXIT = 3 };
             u32 phase = PH_FRAME;
             u32 st = 0;
@@ -2483,19 +2497,19 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
                 u32 *dst = (u32 *)&s;
                 for (u32 w = lane; w < BRX_LDS_BYTES / 4u; w += 64u) dst[w] = rec->lds[w];
                 if (lane == 0u) { // the output window has moved: same bytes, new base (a multiple of 16 away) and capacity
-                    const u64 op = (u64)(uintptr_t)(a.out + o0);
+                    const u64 op = (u64)(uintptr_t)(a_out + o0);
                     const u64 capacity = o1 >= o0 ? o1 - o0 : 0ull;
                     const u32 cap = capacity > 0xffffff00ull ? 0xffffff00u : (u32)capacity;
                     s.st[7] = (u32)op; s.st[8] = (u32)(op >> 32); s.st[9] = cap;
                     // ... and so may the input window have (BrxResume::in_slide): new base / end, the cursor relative to it; the
                     // loop watchdog counts per slice (its limit follows from what is resident)
-                    const u8 *inp = a.in + i0;
+                    const u8 *inp = a_in + i0;
                     const u32 mis = (u32)((uintptr_t)inp & 3u);
                     const u64 iw = (u64)(uintptr_t)(inp - mis), in_len = i1 >= i0 ? i1 - i0 : 0ull;
                     s.st[0] = (u32)iw; s.st[1] = (u32)(iw >> 32); s.st[2] = (u32)((mis + in_len + 3u) >> 2);
                     const u64 be = 8ull * (mis + in_len);
                     s.st[5] = (u32)be; s.st[6] = (u32)(be >> 32);
-                    const u64 bp = ((u64)s.st[3] | ((u64)s.st[4] << 32)) - 8ull * rec->in_slide;
+                    const u64 bp = ((u64)s.st[3] | ((u64)s.st[4] << 32)) - 8ull * (rd != nullptr ? rd->in_slide : rec->in_slide);
                     s.st[3] = (u32)bp; s.st[4] = (u32)(bp >> 32);
                     s.st[29] = 0u; s.st[30] = 0u;
                     const u64 wdl = 8ull * in_len + (u64)cap + 65536ull;
@@ -2504,8 +2518,8 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
                 phase = rfl(rec->phase);
                 st = (phase == PH_LOOP || phase == PH_ASMEXIT) ? HC_CONTINUE : 0u;
             }
-            const u64 pause_at = rec->pause_at, in_low = rec->in_low;
-            const bool no_mb_pause = rec->need_room == 1ull; // (on the way in: the host could not make room for a whole meta-block before)
+            const u64 pause_at = rd != nullptr ? rd->pause_at : rec->pause_at, in_low = rd != nullptr ? rd->in_low : rec->in_low;
+            const bool no_mb_pause = (rd != nullptr ? rd->room_in : rec->need_room) == 1ull; // (on the way in: the host could not make room for a whole meta-block before)
             bool room_optional = false;
             if (lane == 0u) {
                 s.st[ST_PAUSE_AT] = (u32)pause_at; s.st[ST_PAUSE_AT + 1] = (u32)(pause_at >> 32);
@@ -2605,12 +2619,20 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
                 st = BRX_PAUSED;
             } else {
                 const u32 *slab = (const u32 *)(uintptr_t)get64(s, 20);
-                if (slab != nullptr) scratch_release(a.pool, slab);
+                if (slab != nullptr) scratch_release(a_pool, slab);
                 if (lane == 0u) rec->state = 2u;
             }
             if (lane == 0u) {
-                a.status[sid] = (int)final_status(st);
-                a.out_len[sid] = st == ST_OUTPUT_TOO_SMALL ? (u64)rfl(s.st[22]) : (u64)rfl(s.st[10]);
+                const u64 olen = st == ST_OUTPUT_TOO_SMALL ? (u64)rfl(s.st[22]) : (u64)rfl(s.st[10]);
+                if (rd != nullptr) { // (everything the host needs of the slice in the stream's line of the table)
+                    rd->out_len = olen;
+                    rd->need_room = paused ? (u64)need_room | (room_optional ? 1ull << 63 : 0ull) : 0ull;
+                    rd->cursor = get64(s, 3);
+                    rd->status = (int)final_status(st);
+                } else {
+                    a.status[sid] = (int)final_status(st);
+                    a.out_len[sid] = olen;
+                }
             }
             continue;
         }

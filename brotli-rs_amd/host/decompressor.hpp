@@ -125,6 +125,16 @@ template <class R> class Decompressor {
         return (size_t)n;
     }
 
+    // Decoded bytes read() hands out without decoding anything (brx_stream_ready): for hosts that move many streams with advance().
+    size_t ready() {
+        prepare();
+        return (size_t)brx_stream_ready(stream_);
+    }
+    brx_stream *handle() { // (prepared)
+        prepare();
+        return stream_;
+    }
+
     std::vector<uint8_t> read_to_end() {
         std::vector<uint8_t> out;
         uint8_t tmp[65536];
@@ -132,5 +142,19 @@ template <class R> class Decompressor {
         return out;
     }
 };
+
+// Many Decompressors on ONE thread (an event loop over sockets): every one that is pulled (its input did not end within the first
+// POOLED_LIMIT bytes), unfinished and has nothing left to read moves on by one slice, all of those slices in shared launches
+// (brx_stream_advance; reader rounds in brx.h).  The others are left alone: read() serves them as before.  All must be on
+// default_context().  Returns how many moved on.
+template <class D> size_t advance(D *const *ds, size_t n) {
+    std::vector<brx_stream *> h;
+    h.reserve(n);
+    for (size_t i = 0; i < n; i++) h.push_back(ds[i]->handle());
+    const int rc = brx_stream_advance(h.data(), (uint32_t)h.size());
+    if (rc < 0) throw std::runtime_error(std::string("brx_stream_advance: ") + brx_last_error());
+    return (size_t)rc;
+}
+template <class D> size_t advance(const std::vector<D *> &ds) { return advance(ds.data(), ds.size()); }
 
 } // namespace brotli

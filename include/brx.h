@@ -151,10 +151,13 @@ enum {
                                      MiB compressed in one go) (default); 0 = no such launch: those meta-blocks run in the C++ loop from a
                                      slab (~3 MB/s per stream).  For callers whose batches are tens of microseconds long and never hold
                                      such streams */
-    BRX_OPTION_READER_MB_ROOM = 14 /* 1 = a bounded / pulled stream pauses in front of a compressed meta-block that does not fit behind its output
+    BRX_OPTION_READER_MB_ROOM = 14, /* 1 = a bounded / pulled stream pauses in front of a compressed meta-block that does not fit behind its output
                                      window and lets the buffer grow to window + meta-block (at most ~34 MiB), so that the fast loop runs it
                                      (default); 0 = such meta-blocks decode command by command in the ~22 MiB buffer (~8 x slower): streams
                                      started afterwards */
+    BRX_OPTION_READER_BATCH = 15  /* 1 = the slices of bounded / pulled streams that are asked for at the same time go out together, one launch
+                                     per round (default; brx_stream_advance, and brx_stream_read on many threads); 0 = every slice is a launch
+                                     of its own, read back from the device (the A/B switch) */
 };
 int brx_ctx_set_option(brx_ctx *ctx, uint32_t option, int64_t value);
 
@@ -209,6 +212,8 @@ const char *brx_last_error(void);
  *   13       slabs of the context's spill pool (896 KiB each; it grows with the launches in flight, to at most what the chip runs at a time)
  *   14, 15   (since the context was made) batches the Read facade launched for queued streams / streams in them: how well the host's
  *            threads coalesce (brx_stream_new below; a status-25 retry counts again)
+ *   16, 17   (since the context was made) slice launches of bounded / pulled streams / slices in them: how well their slices coalesce
+ *            into rounds (brx_stream_advance below; with BRX_OPTION_READER_BATCH = 0 every launch holds one slice)
  */
 double brx_last_timing(brx_ctx *ctx, int which);
 
@@ -281,7 +286,7 @@ typedef struct brx_stream brx_stream;
 brx_stream *brx_stream_new(brx_ctx *ctx, const uint8_t *in, size_t n);
 /* The same object in BOUNDED mode (brx_stream_new picks it by itself for compressed inputs of 4 MiB and more): the stream
  * is decoded slice by slice -- about 4 MiB of output per brx_stream_read that runs dry -- by a resumable kernel into a
- * sliding window on the device, so the output resident at any time is bounded by the largest Brotli window (16 MiB) plus
+ * sliding window on the device (the slices that readers of one context ask for at the same time share a launch: see rounds below), so the output resident at any time is bounded by the largest Brotli window (16 MiB) plus
  * one slice plus slack (~22 MiB) however large the stream (like the reference's Decompressor, whose state is its window,
  * src/lib.rs:377-394, 1560-1567).  Reads see decoded bytes as the slices complete; an invalid stream serves everything
  * decoded before the error.  A single command that produces more than the slack (a > 1 MiB copy, insert or uncompressed
@@ -304,6 +309,29 @@ typedef size_t (*brx_read_fn)(void *user, uint8_t *buf, size_t cap);
 brx_stream *brx_stream_new_reader(brx_ctx *ctx, brx_read_fn read, void *user);
 int64_t brx_stream_read(brx_stream *s, uint8_t *buf, size_t len);
 void brx_stream_free(brx_stream *s);
+/* Rounds (round 7).  A slice is one wavefront's work, so the slices of many bounded / pulled streams of a context run as ONE launch:
+ * a reader round.  Two ways in:
+ *  - Threads: a brx_stream_read that needs a slice queues it; one reader leads a round over everything queued (at most what the chip
+ *    runs at a time, 16 waves per CU; the rest goes out with the next one) while the others wait for their own stream.  Slices are
+ *    long, so the slices asked for while one round runs form the next one.  The leader holds the context's lock only to enqueue a round
+ *    and to settle its results: owners prepare their next slices -- and their pull callbacks run -- while the GPU decodes.
+ *  - brx_stream_advance, for a host that multiplexes many streams on one thread (an event loop over sockets): every listed stream
+ *    that is bounded or pulled, unfinished, and has no decoded bytes left to read moves on by one slice, all of them in shared
+ *    launches; the call returns when they have run.  The others -- streams with bytes to read, finished ones, whole-stream facade
+ *    streams -- are left alone.  All streams must be on one context (else, or for a NULL entry, BRX_ERR_INVALID_ARGUMENT).  Returns how
+ *    many streams it moved on (0: none could), or a BRX_ERR_* code.
+ * Pull callbacks keep their contract: a stream's callback runs on the thread that reads or advances it, with the context's lock
+ * released; the leader of a round never calls another stream's.  A slice decoded in a round is copied to pinned host memory of the
+ * stream's (~5 MiB while it is being read; at most 1 GiB per context, streams beyond read from the device): brx_stream_read serves it
+ * with no HIP call and without the context's lock.  brx_stream_free of a stream whose slice a round is running waits for that round.
+ * BRX_OPTION_READER_BATCH = 0 gives every slice a launch of its own, as before round 7; it may be changed at any time and holds from
+ * the next slice a stream asks for.  A round is not "the most recent launch" of brx_last_timing 2 .. 7, 10 .. 12 and brx_last_trace
+ * (those keep describing the context's batches and single slices, and do not wait for a round); it has a work counter of its own, so
+ * BRX_OPTION_GRID_CAP holds for rounds too. */
+int brx_stream_advance(brx_stream *const *streams, uint32_t n);
+/* Decoded bytes of the stream that brx_stream_read hands out without decoding anything (0 for a whole-stream facade stream that has not
+ * been decoded yet).  No HIP call, no lock: for the thread that owns the stream, e.g. to read between brx_stream_advance calls. */
+int64_t brx_stream_ready(const brx_stream *s);
 
 /* ---- The node: the GPUs of one machine behind ONE call (round 6) ---------------------------------------------
  * Streams are independent -- a reference Decompressor owns all of its state (src/lib.rs:378-394) -- so a batch shards trivially: a
