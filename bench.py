@@ -11,8 +11,14 @@ A "step" = one pass of the hot path (brx_decode_batch through the C ABI) over on
 already resident in HBM.  Workload at every N: BASELINE.json configs[1], "4096 x data/alice29.txt.compressed"
 PER GPU (weak scaling: independent streams shard across ranks with no data-path collective; the RCCL
 scatter/gather of SURVEY 8e lives in brotli-rs_amd/shard.py and is never inside `value`).  Prints ONE JSON line on
-rank 0; next to `value` it carries `strong` (the same 4096-stream batch split over the N GPUs), `kernel_ms_per_rank`, and at
-N = 1 `copy_path` (the LZ77 copy path against the physical HBM roofline: far copies and the two fills of configs 3 / 4).
+rank 0.  A plain run does only what that line's headline needs: set up, warm up, time the K steps, write --dump-outputs,
+check the last step's output (`bit_exact`) and print `value`, `ms_per_step` and `kernel_ms_per_rank`.
+
+--full adds everything else the benchmark measures, after the timed region as before: `strong` (the same 4096-stream batch
+split over the N GPUs) and the RCCL `gather` at N > 1; at rank 0 the CPU baselines, `roofline` (with in-run rocprofv3 PMC
+passes and the single-stream chain floor), at N = 1 `copy_path` (the LZ77 copy path against the physical HBM roofline: far
+copies and the two fills of configs 3 / 4), `configs` and `node_abi`, and the PCIe-inclusive host path.  The --no-* switches
+thin a --full run.
 """
 import argparse
 import json
@@ -602,16 +608,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="alice29x4096", choices=sorted(WORKLOADS))
     ap.add_argument("--streams", type=int, default=0, help="override streams per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-copy-path", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 --pmc passes (roofline.traffic from the committed file)")
-    ap.add_argument("--no-chain-floor", action="store_true", help="skip roofline.chain_floor_ms (the single-stream launches after the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything besides the headline: strong scaling and the gather (N>1), CPU "
+                         "baselines, roofline with PMC traffic and chain floor, copy_path, configs, node_abi, the host path")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (and the host path that goes with them)")
+    ap.add_argument("--no-copy-path", action="store_true", help="--full: skip copy_path")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the in-run rocprofv3 --pmc passes (roofline.traffic from the committed file)")
+    ap.add_argument("--no-chain-floor", action="store_true", help="--full: skip roofline.chain_floor_ms (the single-stream launches after the timed region)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--verify", type=int, default=1)
-    ap.add_argument("--gather", action="store_true", help="also time the ragged gather of the outputs to rank 0 (N>1: always)")
+    ap.add_argument("--gather", action="store_true", help="also time the ragged gather of the outputs to rank 0 (--full at N>1: always)")
     ap.add_argument("--node", choices=["host", "device"], default=None, help="ONE process for all N GPUs through brx_node_decode_batch (the C ABI's node entry) instead of one rank per GPU")
     ap.add_argument("--deal", choices=["ranges", "bytes", "snake"], default="ranges", help="--node: how the batch is dealt over the GPUs")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (config 5's per-GPU share, the cut-stream batch) and `node_abi`")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the `configs` block (config 5's per-GPU share, the cut-stream batch) and `node_abi`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0's batch; see dump_outputs)")
     args = ap.parse_args()
@@ -704,7 +713,7 @@ def main():
     # The RCCL exchange around the decode, timed on its own AFTER the timed region -- never part of `value`:
     # compaction of the capacity slots + grouped send/recv of the ragged outputs to rank 0 (brotli-rs_amd/shard.py).
     gather_info = None
-    if (world > 1 or args.gather) and not STUB:
+    if ((world > 1 and args.full) or args.gather) and not STUB:
         try:
             from brotli_rs_amd import shard
             if world == 1 and not dist.is_initialized():
@@ -733,9 +742,9 @@ def main():
     ok = batch.verify(torch) if args.verify else True
 
     # Strong scaling, the metric as BASELINE.json words it ("a 4096-stream batch at 1/2/4/8 GPUs"): the SAME total batch
-    # split over the ranks, n / N streams per GPU.  At N = 1 it is the weak figure.  Never `value`.
+    # split over the ranks, n / N streams per GPU.  At N = 1 it is the weak figure.  Never `value`; --full only.
     strong = None
-    if world > 1:
+    if world > 1 and args.full:
         ns = max(n // world, 1)
         sb = Batch(torch, np, dev, fx, ns)
         sdt, skms = timed_pass(ctx, sb, args.steps, 1, barrier)
@@ -771,14 +780,15 @@ def main():
         if STUB:
             res["stub"] = "BRX_BENCH_STUB=1: launcher test on CPU, the decode is a stand-in -- `value` means nothing"
             res["data"] = "STUB"
-        if strong is None:
-            strong = {"streams_total": n, "streams_per_gpu": n, "ms_per_step": round(ms_per_step, 4), "value": round(value, 1),
-                      "unit": "MB/s", "note": "N = 1: the strong-scaling batch is the weak one"}
-        strong["what"] = ("the SAME %d-stream batch split over N GPUs (BASELINE.json's metric as worded).  One wavefront decodes one stream, so "
-                          "a GPU's time is bounded below by ONE stream alone (profiles/r04_sweep.txt: 256 .. 4096 x alice29 take 6.6 .. 8.3 ms): "
-                          "N GPUs buy at most that ratio on a 4096-stream batch; throughput scales with N only at >= 4096 streams per GPU "
-                          "(`value`, weak)" % strong["streams_total"])
-        res["strong"] = strong
+        if args.full:
+            if strong is None:
+                strong = {"streams_total": n, "streams_per_gpu": n, "ms_per_step": round(ms_per_step, 4), "value": round(value, 1),
+                          "unit": "MB/s", "note": "N = 1: the strong-scaling batch is the weak one"}
+            strong["what"] = ("the SAME %d-stream batch split over N GPUs (BASELINE.json's metric as worded).  One wavefront decodes one stream, so "
+                              "a GPU's time is bounded below by ONE stream alone (profiles/r04_sweep.txt: 256 .. 4096 x alice29 take 6.6 .. 8.3 ms): "
+                              "N GPUs buy at most that ratio on a 4096-stream batch; throughput scales with N only at >= 4096 streams per GPU "
+                              "(`value`, weak)" % strong["streams_total"])
+            res["strong"] = strong
         if gather_info:
             if "ms" in gather_info:
                 gather_info["decode_plus_gather_MB_per_s"] = round(total_out / (dt / args.steps + gather_info["ms"] * 1e-3) / 1e6, 1)
@@ -790,9 +800,9 @@ def main():
             dist.destroy_process_group()
         sys.exit(0 if ok else 2)
 
-    # Every collective of this run is behind us.  What follows is rank 0's alone and takes a while (CPU baseline ~12 s, rocprofv3
-    # child passes, single-stream launches): the other ranks must not sit in an RCCL call meanwhile (its watchdog would end the job) --
-    # the group is taken down HERE, together, and they leave.  (VERDICT r4 #6b)
+    # Every collective of this run is behind us.  What follows is rank 0's alone and, with --full, takes a while (CPU baseline ~12 s,
+    # rocprofv3 child passes, single-stream launches): the other ranks must not sit in an RCCL call meanwhile (its watchdog would end the
+    # job) -- the group is taken down HERE, together, and they leave.  (VERDICT r4 #6b)
     used_rccl = dist.is_initialized()
     if used_rccl:
         try:
@@ -806,7 +816,7 @@ def main():
         sys.stderr.flush()
         os._exit(0 if ok else 2)  # (no interpreter teardown: RCCL's destructor prints to stdout, the contract is ONE JSON line)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         import oracle_py
         cb = None
         if not args.no_cpu_baseline:
@@ -889,7 +899,7 @@ def main():
             res["roofline"]["physical_model"] = "PMC traffic (FETCH_SIZE + WRITE_SIZE)"
     del batch
     torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_copy_path and world == 1:
             try:
                 res["copy_path"] = copy_path(torch, np, dev, ctx, barrier)

@@ -22,7 +22,7 @@ def _run(args, stub):
 
 
 def test_gpus_2_starts_two_ranks():
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "monkeyx16384", "--streams", "8"], stub=True)
+    r = _run(["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--workload", "monkeyx16384", "--streams", "8"], stub=True)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -34,6 +34,29 @@ def test_gpus_2_starts_two_ranks():
     assert len(res["strong"]["kernel_ms_per_rank"]) == 2 and res["strong"]["unit"] == "MB/s" and "what" in res["strong"]
     assert res["steps"] == 2 and res["warmup"] == 1 and res["higher_is_better"] is True and res["vs_baseline"] is None
     assert "poisoned" in res["bit_exact_of"]
+
+
+EXTRAS = ("strong", "gather", "roofline", "copy_path", "configs", "node_abi", "host_path_pcie_inclusive", "config1", "cpu_baseline",
+          "speedup_vs_cpu_1core", "cpu_libbrotlidec", "cpu_all_cores")
+
+
+def test_plain_run_prints_the_headline_alone():
+    """Without --full a run times its steps and prints the headline line: nothing measured besides it, at N = 1 and N = 2; with
+    --full the N = 1 line carries `strong` again."""
+    for gpus in ("1", "2"):
+        r = _run(["--gpus", gpus, "--steps", "2", "--warmup", "1", "--workload", "monkeyx16384", "--streams", "8"], stub=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        assert res["n_gpus"] == int(gpus) and len(res["kernel_ms_per_rank"]) == int(gpus) and res["steps"] == 2 and res["warmup"] == 1
+        assert res["unit"] == "MB/s" and res["higher_is_better"] is True and res["dtype"] == "u8" and res["bit_exact"] is True
+        assert res["value"] > 0 and res["ms_per_step"] > 0 and res["metric"] == "decompressed MB/s (whole node), monkeyx16384 batch"
+        assert not [k for k in EXTRAS if k in res], res
+    r = _run(["--gpus", "1", "--full", "--steps", "2", "--warmup", "1", "--workload", "monkeyx16384", "--streams", "8"], stub=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert res["strong"]["streams_per_gpu"] == 8 and res["strong"]["ms_per_step"] == res["ms_per_step"]
 
 
 def test_gpus_2_without_two_gpus_fails_loudly():

@@ -9,7 +9,7 @@ for r in $(seq ${ROUNDS:-2}); do
     cp $so brotli-rs_amd/libbrx.so
     for spec in ${WLS:-alice29x4096 config5_1MiBx1024}; do
       wl=${spec%%:*}; n=${spec#*:}; [ "$n" = "$spec" ] && n=""
-      timeout 300 python bench.py --workload $wl ${n:+--streams $n} --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-traffic --no-copy-path --no-chain-floor 2>&1 | tail -1 > /tmp/l.json
+      timeout 300 python bench.py --full --workload $wl ${n:+--streams $n} --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-traffic --no-copy-path --no-chain-floor 2>&1 | tail -1 > /tmp/l.json
       python - $so $spec <<'PY'
 import sys,json
 try:

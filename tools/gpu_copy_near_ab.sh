@@ -6,7 +6,7 @@ for defs in "COPY_NEAR_MAX=512" ""; do
   echo "=== [$defs]"
   python tools/gpu_fixture_rates.py 4096 2>/dev/null > /tmp/rates_$([ -z "$defs" ] && echo new || echo old).txt
   for wl in alice29x4096 compressed_repeatedx4096 monkeyx16384; do
-    python bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-traffic --no-copy-path --no-configs 2>/dev/null | tail -1 > /tmp/ab.json
+    python bench.py --full --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-traffic --no-copy-path --no-configs 2>/dev/null | tail -1 > /tmp/ab.json
     python -c "import json;d=json.load(open('/tmp/ab.json'));print('%-26s kernel %.4f ms exact %s' % ('$wl',d['roofline']['kernel_ms_avg'],d['bit_exact']))"
   done
 done

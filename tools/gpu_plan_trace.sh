@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for v in ${VARIANTS:-BRX_PLAN_B=1 BRX_PLAN_A=1}; do
   rm -rf /tmp/kt; echo "== variant: ${v:-default}  workload ${WL:-mixed_textx4096}"
-  env $v timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o t -- python $R/bench.py --workload ${WL:-mixed_textx4096} --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --no-copy-path --no-chain-floor 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms_avg'], 'bit_exact', d['bit_exact'])"
+  env $v timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o t -- python $R/bench.py --full --workload ${WL:-mixed_textx4096} --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --no-copy-path --no-chain-floor 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', d['ms_per_step'], 'kernel_ms', d['roofline']['kernel_ms_avg'], 'bit_exact', d['bit_exact'])"
   python3 - <<'PY'
 import csv,glob
 rows=[]
