@@ -23,6 +23,8 @@ OK = 0
 OUTPUT_TOO_SMALL = 25
 REF_PANIC = 26
 
+DIGEST_KINDS = {"crc32": 1, "crc32c": 2}  # BRX_DIGEST_*
+
 
 class BrxError(RuntimeError):
     pass
@@ -72,6 +74,9 @@ def load_library():
     L.brx_compact_batch.restype = ctypes.c_int
     L.brx_compact_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    L.brx_digest_batch.restype = ctypes.c_int
+    L.brx_digest_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -127,7 +132,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_host_alloc", "brx_host_free", "brx_stream_new_bounded", "brx_generate_batch", "brx_compact_batch",
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
-                    "brx_stream_advance", "brx_stream_ready"]
+                    "brx_stream_advance", "brx_stream_ready", "brx_digest_batch"]
 
 
 def status_str(code: int) -> str:
@@ -262,6 +267,32 @@ class Context:
         rc = self._lib.brx_compact_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, dst_ptr, dst_off_ptr, total, hip_stream)
         if rc != 0:
             raise BrxError("brx_compact_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def digest_batch_device(self, kind, out_ptr, out_off_ptr, len_ptr, n, digest_ptr, expect_ptr=None, mismatch_ptr=None, hip_stream=None):
+        """brx_digest_batch on raw device pointers: digest[i] = CRC-32 (kind 1) / CRC-32C (kind 2) of out[out_off[i] .. + len[i])."""
+        rc = self._lib.brx_digest_batch(self._h, kind, out_ptr, out_off_ptr, len_ptr, n, digest_ptr, expect_ptr, mismatch_ptr, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_digest_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def digest_batch(self, out, out_off, out_len, kind="crc32", expect=None, stream=None):
+        """CRC-32 / CRC-32C ("crc32" / "crc32c") of the decoded streams of a batch, on the device.  out: uint8 device tensor;
+        out_off: int64 device tensor, the first len(out_len) entries are used; out_len: int64 device tensor, the entries of failed
+        streams zeroed.  Returns the digests (int32 tensor holding the 32-bit patterns: `& 0xFFFFFFFF` after .tolist()), and with
+        `expect` (same layout) also the mismatch tensor (1 where a digest differs, else 0).  stream: a torch.cuda.Stream the work
+        is enqueued on (no synchronisation); None = the context's own stream, and the call returns when the digests are there."""
+        import torch
+        n = int(out_len.numel())
+        digest = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)
+        mismatch = torch.empty(max(n, 1), dtype=torch.int32, device=out.device) if expect is not None else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        self.digest_batch_device(DIGEST_KINDS[kind], out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, digest.data_ptr(),
+                                 expect.data_ptr() if expect is not None else None,
+                                 mismatch.data_ptr() if mismatch is not None else None,
+                                 stream.cuda_stream if stream is not None else None)
+        if expect is not None:
+            return digest[:n], mismatch[:n]
+        return digest[:n]
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

@@ -28,6 +28,7 @@
 #include "../../include/brx.h"
 #include "_gen/brx_tables_gen.h" // BRX_DICT, BRX_CONTEXT_LUT, BRX_TRANSFORMS  (tools/bin2h.py from tables/*.bin)
 #include "brx_device.h"
+#include "brx_digest.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -66,6 +67,7 @@ static int fail(int code, const char *what, hipError_t e = hipSuccess) {
     }
 
 #define BRX_COUNTER_RING 64u   // launches in flight on one context before a work counter is reused
+#define BRX_DIGEST_RING 16u   // brx_digest_batch launches in flight on one context before a scratch region is reused (the call then waits)
 #define BRX_MAX_CHUNKS 8u      // host-pointer pipeline: H2D / decode / D2H chunks in flight
 #define BRX_STREAM_LIMIT 0xffffff00ull // per-stream output limit of the 32-bit position arithmetic
 
@@ -169,6 +171,14 @@ struct brx_ctx {
     hipEvent_t ev_prep = nullptr;
     BrxReaderDesc *h_rdesc = nullptr, *d_rdesc = nullptr; // max_grid descriptors: pinned host table, device table
     uint64_t reader_launches = 0, reader_slices = 0; // slice launches of bounded / pulled streams / slices in them (brx_last_timing 16 / 17)
+    // brx_digest_batch (brx_digest.hip): the table block of each kind, built by the host on first use; scratch of BRX_DIGEST_RING
+    // launches (ticket counter, tile prefix sums, per-stream accumulators), every launch in a region of its own
+    uint32_t *d_digest_tab[2] = {nullptr, nullptr};
+    uint8_t *d_digest_scratch = nullptr;
+    size_t digest_cap = 0;                        // streams one region holds
+    uint64_t digest_seq = 0;
+    hipEvent_t ev_digest[BRX_DIGEST_RING] = {};   // recorded behind the launch that used the region
+    bool digest_used[BRX_DIGEST_RING] = {};
     std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
     std::vector<uint8_t *> stage_free;
     size_t stage_bytes = 0;
@@ -252,6 +262,10 @@ static void ctx_release(brx_ctx *c) {
     (void)hipFree(c->st_meta);
     (void)hipFree(c->d_gen_header);
     (void)hipFree(c->st_gen);
+    for (auto &t : c->d_digest_tab) (void)hipFree(t);
+    (void)hipFree(c->d_digest_scratch);
+    for (auto &ev : c->ev_digest)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_in)
@@ -1198,6 +1212,68 @@ extern "C" int brx_compact_batch(brx_ctx *c, const uint8_t *out, const uint64_t 
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     brx_launch_compact(out, out_off, len, dst, dst_off, n, total, st);
     HIP_TRY(hipGetLastError());
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- CRC-32 / CRC-32C of the decoded streams of a batch (brx_digest.hip) ---------------------------------------------------
+void brx_launch_digest(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, const uint32_t *tab, uint32_t poly,
+                       void *scratch, uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, unsigned workgroups, void *hip_stream);
+
+static size_t digest_region_bytes(size_t cap) { return (128u + (cap + 1u) * 8u + cap * 4u + 127u) & ~(size_t)127u; }
+
+extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                                uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_digest_batch: ctx is NULL");
+    if (kind != BRX_DIGEST_CRC32 && kind != BRX_DIGEST_CRC32C) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_digest_batch: unknown kind");
+    if (!digest) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_digest_batch: digest is NULL");
+    if ((expect == nullptr) != (mismatch == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_digest_batch: expect and mismatch go together");
+    if (n == 0) return BRX_SUCCESS;
+    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_digest_batch: NULL table");
+    const uint32_t poly = kind == BRX_DIGEST_CRC32 ? 0xEDB88320u : 0x82F63B78u;
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        uint32_t *&tab = c->d_digest_tab[kind - 1u];
+        if (!tab) { // first use of this kind on this context: tables from the polynomial, by the host
+            std::vector<uint32_t> h(BRX_DG_WORDS);
+            brx_dg_build_tables(poly, h.data());
+            uint32_t *d = nullptr;
+            hipError_t e = hipMalloc(&d, BRX_DG_WORDS * 4u);
+            if (e != hipSuccess) return fail(BRX_ERR_OUT_OF_MEMORY, "digest table allocation failed", e);
+            e = hipMemcpy(d, h.data(), BRX_DG_WORDS * 4u, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(d);
+                return fail(BRX_ERR_HIP, "digest table upload failed", e);
+            }
+            tab = d;
+        }
+        if (n > c->digest_cap || !c->d_digest_scratch) {
+            // (rare) a larger scratch: launches on any stream may still use the old one
+            HIP_TRY(hipDeviceSynchronize());
+            for (auto &u : c->digest_used) u = false;
+            (void)hipFree(c->d_digest_scratch);
+            c->d_digest_scratch = nullptr;
+            c->digest_cap = 0;
+            const size_t cap = (size_t)n + n / 4u + 1024u;
+            hipError_t e = hipMalloc(&c->d_digest_scratch, digest_region_bytes(cap) * BRX_DIGEST_RING);
+            if (e != hipSuccess) return fail(BRX_ERR_OUT_OF_MEMORY, "digest scratch allocation failed", e);
+            c->digest_cap = cap;
+        }
+        const unsigned slot = (unsigned)(c->digest_seq++ % BRX_DIGEST_RING);
+        if (!c->ev_digest[slot]) HIP_TRY(hipEventCreateWithFlags(&c->ev_digest[slot], hipEventDisableTiming));
+        if (c->digest_used[slot]) HIP_TRY(hipEventSynchronize(c->ev_digest[slot])); // the launch that had this region 16 calls ago
+        void *scratch = c->d_digest_scratch + digest_region_bytes(c->digest_cap) * slot;
+        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU, 80 of its 160 KiB of LDS (max_grid = 16 per CU)
+        brx_launch_digest(out, out_off, len, n, tab, poly, scratch, digest, expect, mismatch, c->max_grid / 4u, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_digest[slot], st));
+        c->digest_used[slot] = true;
+    }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)

@@ -271,6 +271,28 @@ int brx_generate_batch(brx_ctx *ctx, const uint8_t *src, const uint64_t *src_off
 int brx_compact_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
                       uint8_t *dst, const uint64_t *dst_off, uint64_t total, void *hip_stream);
 
+/* ---- checksums of the decoded bytes of a batch (device memory only) --------------------------------------
+ * Brotli carries no checksum; the containers around it keep one of the DECODED bytes, nearly always one of these two.  A batch
+ * that stays on the device is verified there: nothing but the digests (or n mismatch words) ever crosses to the host.
+ *   digest[i] = CRC of out[out_off[i] .. out_off[i] + len[i])                                   for i < n
+ * `len` is brx_decode_batch's out_len (zero the entries of failed streams first), exactly as for brx_compact_batch; len[i] = 0
+ * gives 0, the CRC of the empty string.  Bytes of a slot beyond len[i] never enter the result; out_off needs no alignment; len[i]
+ * runs up to the per-stream limit (4 GiB - 256 B).  All pointers are DEVICE memory.
+ *   expect / mismatch   both NULL, or both n entries: mismatch[i] = 1 where digest[i] != expect[i], else 0.  No total is written
+ *                       (there is no mismatch[n]): the caller sums the array -- one n-word readback verifies a batch.
+ * hip_stream NULL = the context's own stream and the call returns when the digests are there; otherwise it is enqueued (behind a
+ * brx_decode_batch on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.
+ * Scratch (per-stream accumulators, tile prefix sums, a ticket counter) belongs to the context, every launch has a region of its
+ * own, so calls on different HIP streams of one context may overlap; a call with a larger n than any before synchronises the
+ * device once to grow it, and the 17th call in flight waits on the host for the first.  The tables are built by the host from the
+ * generator polynomial the first time a context uses a kind (one blocking 28 KiB upload).
+ * BRX_ERR_INVALID_ARGUMENT: an unknown kind, digest NULL, only one of expect / mismatch.  n = 0 returns BRX_SUCCESS, no launch.
+ * One pass over the bytes (reads sum(len), writes 4 n); no reference counterpart. */
+#define BRX_DIGEST_CRC32 1u  /* reflected 0xEDB88320, init / xorout 0xFFFFFFFF: zlib, gzip, zip, PNG */
+#define BRX_DIGEST_CRC32C 2u /* reflected 0x82F63B78, same init / xorout: iSCSI, ext4, most object stores */
+int brx_digest_batch(brx_ctx *ctx, uint32_t kind, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                     uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one
