@@ -318,11 +318,11 @@ static int ctx_init(brx_ctx *c, int device) {
     HIP_TRY(hipMalloc(&c->d_dict, sizeof BRX_DICT));
     HIP_TRY(hipMalloc(&c->d_lut, sizeof BRX_CONTEXT_LUT));
     HIP_TRY(hipMalloc(&c->d_xforms, 121 * sizeof(BrxTransform)));
-    HIP_TRY(hipMalloc(&c->d_counters, (BRX_COUNTER_RING + 1u) * 128u));
-    HIP_TRY(hipHostMalloc((void **)&c->h_handed, 16 + 64 * BRX_COUNTER_RING, hipHostMallocMapped)); // (word 0: handed_seq; from word 4: 16 words per launch slot, plan B's counts)
+    HIP_TRY(hipMalloc(&c->d_counters, (BRX_COUNTER_RING + 1u) * BRX_WC_WORDS * 4u));
+    HIP_TRY(hipHostMalloc((void **)&c->h_handed, (BRX_HC_BASE + BRX_HC_SLOT_WORDS * BRX_COUNTER_RING) * 4u, hipHostMallocMapped)); // (word 0: handed_seq; then a block per launch slot, plan B's counts: brx_device.h, BRX_HC_*)
     *c->h_handed = 0u;
     HIP_TRY(hipHostGetDevicePointer((void **)&c->d_handed, c->h_handed, 0));
-    HIP_TRY(hipMemset(c->d_counters, 0, (BRX_COUNTER_RING + 1u) * 128u));
+    HIP_TRY(hipMemset(c->d_counters, 0, (BRX_COUNTER_RING + 1u) * BRX_WC_WORDS * 4u));
     HIP_TRY(hipMalloc(&c->d_pool, sizeof(BrxSlabPool)));
     HIP_TRY(hipMemset(c->d_pool, 0, sizeof(BrxSlabPool)));
     HIP_TRY(hipMemcpy(c->d_dict, BRX_DICT, sizeof BRX_DICT, hipMemcpyHostToDevice));
@@ -565,6 +565,10 @@ static int ensure_defer(brx_ctx *c, uint32_t n) {
     return BRX_SUCCESS;
 }
 
+// The decode kernel's launcher by level (brx_device.h).
+static void (*const brx_launch_level[BRX_LEVELS])(const BrxKernelArgs &, unsigned, void *) = {
+    brx_launch_decode, brx_launch_decode_l1, brx_launch_decode_l2, brx_launch_decode_l3, brx_launch_decode_l4};
+
 // Room for one queue order of n stream indices per launch in flight (BRX_OPT_ORDER, device path).
 static int ensure_order(brx_ctx *c, uint32_t n) {
     if (c->d_order && c->order_cap >= n) return BRX_SUCCESS;
@@ -580,62 +584,63 @@ static int ensure_order(brx_ctx *c, uint32_t n) {
     return BRX_SUCCESS;
 }
 
-static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n,
-                  uint8_t *d_out, const uint64_t *d_out_off, uint64_t *d_out_len, int32_t *d_status,
-                  const uint32_t *d_order = nullptr, BrxResume *d_resume = nullptr, const BrxSlabPool *d_own_pool = nullptr,
-                  uint8_t *d_out_mirror = nullptr, bool may_plan_b = false, uint32_t n_large = 0xffffffffu,
-                  BrxReaderDesc *d_desc = nullptr) {
-    BrxKernelArgs a;
-    const bool resumable = d_resume != nullptr || d_desc != nullptr; // (d_desc: a reader round, every stream in buffers of its own)
-    a.rdesc = d_desc;
-    a.out_mirror = d_out_mirror;
-    a.order = d_order;
-    a.in = d_in;
-    a.in_off = d_in_off;
-    a.out = d_out;
-    a.out_off = d_out_off;
-    a.out_len = d_out_len;
-    a.status = d_status;
+// What one launch() decodes.  A caller sets what it means; the rest keeps these defaults.
+struct LaunchReq {
+    const uint8_t *in = nullptr;       // the batch: n streams in one input and one output buffer, by offset tables ...
+    const uint64_t *in_off = nullptr;
+    uint32_t n = 0;
+    uint8_t *out = nullptr;
+    const uint64_t *out_off = nullptr;
+    uint64_t *out_len = nullptr;
+    int32_t *status = nullptr;
+    BrxReaderDesc *desc = nullptr;     // ... or a reader round: n streams in buffers of their own, one descriptor each
+    const uint32_t *order = nullptr;   // queue order (BrxKernelArgs::order), and
+    uint32_t n_large = 0xffffffffu;    // ... where the small streams, the order's tail, start in it (none: the lean kernel classifies)
+    BrxResume *resume = nullptr;       // one stream's slice: its state record, and
+    const BrxSlabPool *own_pool = nullptr; // ... its own one-slab pool instead of the context's
+    uint8_t *out_mirror = nullptr;     // BrxKernelArgs::out_mirror
+    bool timing = false;               // record the events of brx_last_timing around the kernels
+    bool may_plan_b = false;           // the call may wait for a pre-pass (launch plan B)
+};
+
+static int launch(brx_ctx *c, hipStream_t st, const LaunchReq &r) {
+    const uint32_t n = r.n;
+    BrxKernelArgs a{}; // (everything a launch does not use stays nullptr / 0)
+    const bool resumable = r.resume != nullptr || r.desc != nullptr; // (r.desc: a reader round, every stream in buffers of its own)
+    a.rdesc = r.desc;
+    a.out_mirror = r.out_mirror;
+    a.order = r.order;
+    a.in = r.in;
+    a.in_off = r.in_off;
+    a.out = r.out;
+    a.out_off = r.out_off;
+    a.out_len = r.out_len;
+    a.status = r.status;
     a.n = n;
     a.debug_stop = c->debug_stop;
     unsigned grid = n < c->max_grid ? n : c->max_grid;
     if (c->grid_cap != 0u && grid > c->grid_cap) grid = c->grid_cap; // (A/B knob BRX_GRID_CAP: fewer resident waves, more rounds)
-    a.pool = d_own_pool;
+    a.pool = r.own_pool;
     // (what this launch runs at a time: its regular grid; under plan B the wider grids next to it -- together never more than its
     // streams, nor than the chip holds; the grid-cap knob caps each of the four grids)
-    const bool can_plan_b = may_plan_b && !c->no_defer && !c->no_plan_b && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS;
-    const unsigned slab_waves = (d_own_pool || d_desc) ? 0u : (c->grid_cap != 0u && can_plan_b) ? std::min(n, 4u * c->grid_cap) : grid;
-    if (!d_own_pool && !d_desc) { // (a round's streams have their own pools: BrxReaderDesc::pool)
+    const bool can_plan_b = r.may_plan_b && !c->no_defer && !c->no_plan_b && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS;
+    const unsigned slab_waves = (r.own_pool || r.desc) ? 0u : (c->grid_cap != 0u && can_plan_b) ? std::min(n, 4u * c->grid_cap) : grid;
+    if (!r.own_pool && !r.desc) { // (a round's streams have their own pools: BrxReaderDesc::pool)
         int rc = ensure_pool(c, pool_need(c, slab_waves));
         if (rc) return rc;
         a.pool = c->d_pool;
     }
-    a.resume = d_resume;
+    a.resume = r.resume;
     // which build of the command loop (brx_hot.S): with at most BRX_SW_WAVES_PER_CU streams per CU the CU's scalar ALU has
     // room and the build with the shorter dependent chain wins; fuller CUs take the one that spares the scalar ALU
     a.loop_build = c->loop_build >= 0 ? (uint32_t)c->loop_build : (grid <= c->max_grid / 16u * BRX_SW_WAVES_PER_CU ? 1u : 0u);
     const size_t ring_slot = (size_t)(c->launch_seq++ % BRX_COUNTER_RING);
     // one 128-B line per launch; a reader round -- hundreds of ms on a HIP stream of its own while batches go on -- has a line of its own
     // that no later launch can take over (rounds run one at a time)
-    a.work_counter = c->d_counters + (d_desc ? (size_t)BRX_COUNTER_RING : ring_slot) * 32u;
+    a.work_counter = c->d_counters + (r.desc ? (size_t)BRX_COUNTER_RING : ring_slot) * BRX_WC_WORDS;
     // streams whose tables spill a kernel's LDS table memory are listed for the level that holds them (not in the resumable and
     // bring-up modes): BrxKernelArgs::defer
     a.tiny_bytes = c->tiny_bytes;
-    a.defer = nullptr;
-    a.defer_cap = 0;
-    a.handup = nullptr;
-    a.late_cap = 0;
-    a.handup2 = nullptr;
-    a.late2_cap = 0;
-    a.cls = nullptr;
-    a.prepass = 0u;
-    a.list_mask = 0u;
-    a.counter_idx = 0u;
-    a.late_only = 0u;
-    a.big_bytes = 0u;
-    a.start_total = 0u;
-    a.start_value = 0u;
-    a.start_flag = nullptr;
     a.sw_threshold = c->loop_build >= 0 ? 0u : c->max_grid / 16u * BRX_SW_WAVES_PER_CU;
     uint32_t *regions = nullptr; // this launch's BRX_LIST_REGIONS regions of defer_cap words
     if (!c->no_defer && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS) {
@@ -653,30 +658,26 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
     }
     // The lean instance in front (brx_small.h; 32 waves per CU): it decodes the streams of at most BRX_SMALL_STREAM_BYTES
     // compressed bytes and lists the rest -- and what it gives up on -- for the regular kernel (BrxKernelArgs::s_list).  With a
-    // queue order from the host (longest first) the small streams are the order's tail: `n_large` says where it starts, the
+    // queue order from the host (longest first) the small streams are the order's tail: `r.n_large` says where it starts, the
     // regular kernel keeps the head as its own queue.  Without one the lean kernel classifies all n streams itself and the
     // regular kernel's whole queue is that list.
-    a.s_list = nullptr;
     a.small_bytes = c->small_bytes;
-    a.classify = 0u;
     a.n_total = n;
     bool lean = false, lean_tail = false;
-    if (c->small_bytes != 0u && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS && (d_order == nullptr || n_large < n || n_large == 0xffffffffu)) {
+    if (c->small_bytes != 0u && !resumable && c->debug_stop == 0u && n <= BRX_DEFER_MAX_STREAMS && (r.order == nullptr || r.n_large < n || r.n_large == 0xffffffffu)) {
         int rc = ensure_defer(c, n);
         if (rc) return rc;
         a.s_list = c->d_defer + (ring_slot * BRX_LIST_REGIONS + 4u) * c->defer_cap;
-        lean_tail = d_order != nullptr && n_large <= n; // (else: the lean kernel classifies, the regular one takes the list)
+        lean_tail = r.order != nullptr && r.n_large <= n; // (else: the lean kernel classifies, the regular one takes the list)
         if (lean_tail) {
-            a.n = n_large;
+            a.n = r.n_large;
         } else {
             a.order = nullptr;
             a.n = 0u;
         }
         lean = true;
     }
-    a.debug = nullptr;
-    a.trace = nullptr;
-    if (c->trace_on && !d_desc) { // diagnostics: one record per stream (of batches and single slices; a reader round records none)
+    if (c->trace_on && !r.desc) { // diagnostics: one record per stream (of batches and single slices; a reader round records none)
         if (c->trace_cap < n) {
             HIP_TRY(hipDeviceSynchronize());
             (void)hipFree(c->d_trace);
@@ -689,7 +690,6 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
         a.trace = c->d_trace;
         c->trace_n = n;
     }
-    a.dump = nullptr;
     a.dump_interval = c->dump_interval;
     a.dump_max = c->dump_max;
 #ifdef BRX_BRINGUP // (build.py with BRX_BRINGUP=1: per-stream statistics, LDS dumps for tools/asm_emu.py)
@@ -721,14 +721,14 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
     a.handed_seq = c->d_handed;
     const uint32_t seen = c->h_handed ? *(volatile uint32_t *)c->h_handed : 0u;
     const bool lately = c->force_plan_b || (seen != 0u && a.launch_seq - seen <= 64u);
-    const bool plan_b = a.defer != nullptr && may_plan_b && !c->no_plan_b && lately;
-    HIP_TRY(hipMemsetAsync(a.work_counter, 0, 128, st));
-    if (timing) HIP_TRY(hipEventRecord(c->ev[2], st));
+    const bool plan_b = a.defer != nullptr && r.may_plan_b && !c->no_plan_b && lately;
+    HIP_TRY(hipMemsetAsync(a.work_counter, 0, BRX_WC_WORDS * 4, st));
+    if (r.timing) HIP_TRY(hipEventRecord(c->ev[2], st));
     if (lean) {
         BrxKernelArgs as = a;
         if (lean_tail) { // the order's tail
-            as.order = d_order + n_large;
-            as.n = n - n_large;
+            as.order = r.order + r.n_large;
+            as.n = n - r.n_large;
         } else {
             as.n = n;
             as.classify = 1u;
@@ -741,7 +741,7 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
         BrxKernelArgs ap = a;
         ap.cls = (uint8_t *)(regions + 5u * c->defer_cap);
         ap.prepass = 1u;
-        ap.counter_idx = 9u;
+        ap.counter_idx = BRX_WC_TICKETS_PRE;
         brx_launch_decode(ap, grid, st);
         // The host reads the pre-pass's counts (lists 0..2, and how many streams the lean kernel left to the regular one) and
         // launches exactly the kernels that have work, with exactly their grids: the call waits here for the pre-pass (a header
@@ -749,18 +749,20 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
         // to real ones: a CU's LDS is handed out first-fit, and 10 KiB workgroups that come and go while 20 KiB ones are being
         // placed leave those at offsets between which nothing of their size fits any more (4096 x mapsdatazrh: 6 instead of 8
         // level-2 streams per CU for the whole launch, 89 ms instead of 60).
-        uint32_t *hc = c->h_handed + 4u + 16u * (uint32_t)ring_slot;
-        HIP_TRY(hipMemcpyAsync(hc, a.work_counter + 5, 36, hipMemcpyDeviceToHost, st)); // words 5 .. 13
+        const uint32_t hc_at = BRX_HC_BASE + BRX_HC_SLOT_WORDS * (uint32_t)ring_slot; // this launch's block of the pinned words
+        uint32_t *hc = c->h_handed + hc_at;
+        const auto hcw = [hc](int word) -> uint32_t { return hc[word - BRX_HC_FIRST]; }; // word BRX_WC_x of the counter line, as read back
+        HIP_TRY(hipMemcpyAsync(hc, a.work_counter + BRX_HC_FIRST, (BRX_HC_LAST - BRX_HC_FIRST + 1) * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(c->ev_fork[ring_slot], st));
         HIP_TRY(hipEventSynchronize(c->ev_fork[ring_slot]));
-        const uint32_t cnt[4] = {0u, std::min<uint32_t>(hc[0], n), std::min<uint32_t>(hc[1], n), std::min<uint32_t>(hc[2], n)};
-        const uint32_t queued = a.n + (a.s_list != nullptr ? std::min<uint32_t>(hc[5], n) : 0u); // the regular kernel's queue
+        const uint32_t cnt[4] = {0u, std::min<uint32_t>(hcw(BRX_WC_LIST), n), std::min<uint32_t>(hcw(BRX_WC_LIST + 1), n), std::min<uint32_t>(hcw(BRX_WC_LIST + 2), n)};
+        const uint32_t queued = a.n + (a.s_list != nullptr ? std::min<uint32_t>(hcw(BRX_WC_LEAN_LISTED), n) : 0u); // the regular kernel's queue
         const uint32_t wide = cnt[1] + cnt[2] + cnt[3];
         const uint32_t n0 = queued > wide ? queued - wide : 0u;
         a.cls = ap.cls;
         a.late_only = 1u;
         // the regular kernel's queue, long jobs first without a sort: two walks split at the mean compressed size of its streams
-        a.big_bytes = hc[8] != 0u ? (uint32_t)std::min<uint64_t>(((uint64_t)hc[7] << 6) / hc[8], 0xffffffffull) : 0u;
+        a.big_bytes = hcw(BRX_WC_STAY_N) != 0u ? (uint32_t)std::min<uint64_t>(((uint64_t)hcw(BRX_WC_STAY_UNITS) << 6) / hcw(BRX_WC_STAY_N), 0xffffffffull) : 0u;
         // What is resident together: brx_plan.h (persistent grids that all find room at once, by 40-KiB LDS parts)
         const BrxPlanB plan = brx_plan_b(n0, cnt, c->max_grid / 4u, c->max_grid);
         uint32_t g[4] = {std::min<uint32_t>(plan.grid[0], grid), plan.grid[1], plan.grid[2], plan.grid[3]};
@@ -769,20 +771,20 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
         const uint32_t *mask = plan.mask;
         const int narrowest = g[0] ? 0 : g[1] ? 1 : g[2] ? 2 : 3;
         uint32_t started = 0;
-        hc[12] = 0u;
+        hc[BRX_HC_START_FLAG] = 0u;
         for (int k = 3; k >= 1; k--) {
             if (g[k] == 0u) continue;
             BrxKernelArgs aw = a;
             aw.cls = nullptr;
             aw.list_mask = mask[k];
-            aw.counter_idx = (uint32_t)k;
+            aw.counter_idx = BRX_WC_TICKETS + (uint32_t)k;
             started += g[k];
             aw.start_total = started;
             aw.start_value = (a.launch_seq << 2) | (uint32_t)k;
-            aw.start_flag = k == narrowest ? nullptr : c->d_handed + 4u + 16u * (uint32_t)ring_slot + 12u;
+            aw.start_flag = k == narrowest ? nullptr : c->d_handed + hc_at + BRX_HC_START_FLAG;
             hipStream_t sw = k == narrowest ? st : c->s_wide[k - 1];
             if (sw != st) HIP_TRY(hipStreamWaitEvent(sw, c->ev_fork[ring_slot], 0));
-            if (k == 1) brx_launch_decode_l1(aw, g[k], sw); else if (k == 2) brx_launch_decode_l2(aw, g[k], sw); else brx_launch_decode_l3(aw, g[k], sw);
+            brx_launch_level[k](aw, g[k], sw);
             if (sw != st) { HIP_TRY(hipEventRecord(c->ev_join[ring_slot][k - 1], sw)); joined[k - 1] = true; }
             if (aw.start_flag != nullptr) {
                 // Widest first, and the next kernel only once this one's workgroups are all resident (its last one to start says
@@ -791,7 +793,7 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
                 // wider kernel then runs BEHIND them (8192 mixed streams: 60 or 110 ms from one launch to the next).  A kernel that
                 // does not report within 2 ms (the chip is busy with somebody else's work) is not waited for any longer.
                 const auto t0 = std::chrono::steady_clock::now();
-                while (*(volatile uint32_t *)&hc[12] != aw.start_value) {
+                while (*(volatile uint32_t *)&hc[BRX_HC_START_FLAG] != aw.start_value) {
                     if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
                 }
             }
@@ -807,13 +809,13 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
         BrxKernelArgs ac = a; // the catch-all: its waves leave at once when nothing is listed
         ac.cls = nullptr;
         ac.list_mask = plan_b ? 8u : 15u;
-        ac.counter_idx = 4u;
+        ac.counter_idx = BRX_WC_TICKETS_ALL;
         // (never more waves than the slab pool has slabs -- ensure_pool(grid) above: a level-3 wave whose stream spills even there
         // holds its slab for the whole decode, and a waiter gives up after 0.5 s: found by the round-5 soak with BRX_GRID_CAP = 64,
         // 199 slab-class streams on a 1024-wave catch-all over 64 slabs, tools/device_fuzz.py 3 302)
         unsigned gc = std::min(n, per_cu * 4u);
         if (c->grid_cap != 0u) gc = std::min(gc, c->grid_cap);
-        brx_launch_decode_l3(ac, gc, st);
+        brx_launch_level[3](ac, gc, st);
         HIP_TRY(hipGetLastError());
         // ... and behind it level 4 (150 KiB of LDS: one workgroup per CU) for what level-3 kernels handed on -- meta-blocks whose tables
         // spill even level 3 (one heterogeneous piece of > 1 MiB from the reference encoder: 10 .. 35 k words).  Its workgroups leave at once
@@ -822,22 +824,22 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
             BrxKernelArgs a4 = a;
             a4.cls = nullptr;
             a4.list_mask = 8u;
-            a4.counter_idx = 20u;
+            a4.counter_idx = BRX_WC_TICKETS_L4;
             unsigned g4 = std::min(n, per_cu);
             if (c->grid_cap != 0u) g4 = std::min(g4, c->grid_cap);
-            brx_launch_decode_l4(a4, g4, st);
+            brx_launch_level[4](a4, g4, st);
             HIP_TRY(hipGetLastError());
         }
     }
-    if (timing) HIP_TRY(hipEventRecord(c->ev[3], st));
+    if (r.timing) HIP_TRY(hipEventRecord(c->ev[3], st));
     // (a reader round is not "the most recent launch" of brx_last_timing / brx_last_trace: it leaves that state alone -- it uses no slab
     // of the context's pool, its counter line is its own, it records no trace)
-    if (!d_desc) HIP_TRY(hipEventRecord(c->ev_last, st));
+    if (!r.desc) HIP_TRY(hipEventRecord(c->ev_last, st));
     if (slab_waves != 0u) {
         HIP_TRY(hipEventRecord(c->ev_done[ring_slot], st));
         c->inflight_waves[ring_slot] = slab_waves;
     }
-    if (!d_desc) c->last_counter = (a.defer != nullptr || lean) ? a.work_counter : nullptr;
+    if (!r.desc) c->last_counter = (a.defer != nullptr || lean) ? a.work_counter : nullptr;
     c->any_launch = true;
 #ifdef BRX_BRINGUP
     if (a.dump) { // bring-up: parked decoder states for tools/asm_emu.py
@@ -846,7 +848,7 @@ static int launch(brx_ctx *c, hipStream_t st, bool timing, const uint8_t *d_in, 
         (void)hipMemcpy(h.data(), a.dump, dump_bytes, hipMemcpyDeviceToHost);
         const uint32_t nrec = std::min(h[0], c->dump_max);
         if (FILE *f = fopen(c->dump_path.c_str(), "ab")) {
-            const uint64_t hdr[4] = {0x31504d5544585242ull /* "BRXDUMP1" */, nrec, (uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out};
+            const uint64_t hdr[4] = {0x31504d5544585242ull /* "BRXDUMP1" */, nrec, (uint64_t)(uintptr_t)r.in, (uint64_t)(uintptr_t)r.out};
             fwrite(hdr, 8, 4, f);
             fwrite(h.data() + 16, 4, (size_t)nrec * BRX_DUMP_WORDS, f);
             fclose(f);
@@ -972,8 +974,14 @@ static int decode_host(brx_ctx *c, const uint8_t *in, const uint64_t *in_off, ui
             n_large = 0;
             for (uint32_t i = a; i < b; i++) n_large += in_off[i + 1] - in_off[i] > (uint64_t)c->small_bytes ? 1u : 0u;
         }
-        rc = launch(c, sk, timing && nchunks == 1, in_dev ? in_dev : c->st_in, d_in_off + a, b - a, c->st_out, d_out_off + a, d_out_len + a,
-                    d_status + a, d_order + a, nullptr, nullptr, mirror, nchunks == 1, n_large);
+        LaunchReq r;
+        r.in = in_dev ? in_dev : c->st_in; r.in_off = d_in_off + a; r.n = b - a;
+        r.out = c->st_out; r.out_off = d_out_off + a; r.out_len = d_out_len + a; r.status = d_status + a;
+        r.order = d_order + a; r.n_large = n_large;
+        r.out_mirror = mirror;
+        r.timing = timing && nchunks == 1;
+        r.may_plan_b = nchunks == 1;
+        rc = launch(c, sk, r);
         if (rc) return rc;
     }
     for (unsigned k = 0; k < nchunks; k++) { // copy out (a second loop: a pageable copy blocks the host until it is done)
@@ -1018,7 +1026,13 @@ static int decode_batch_locked(brx_ctx *c, const uint8_t *in, const uint64_t *in
             for (uint32_t i = 0; i < n; i++) n_large += h[i + 1] - h[i] > (uint64_t)c->small_bytes ? 1u : 0u;
         }
         if (timing) HIP_TRY(hipEventRecord(c->ev[0], st));
-        int rc = launch(c, st, timing, in, in_off, n, out, out_off, out_len, status, d_order, nullptr, nullptr, nullptr, true, n_large);
+        LaunchReq r;
+        r.in = in; r.in_off = in_off; r.n = n;
+        r.out = out; r.out_off = out_off; r.out_len = out_len; r.status = status;
+        r.order = d_order; r.n_large = n_large;
+        r.timing = timing;
+        r.may_plan_b = true;
+        int rc = launch(c, st, r);
         if (rc) return rc;
         if (timing) HIP_TRY(hipEventRecord(c->ev[1], st));
         if (!(opts && opts->hip_stream)) HIP_TRY(hipStreamSynchronize(st));
@@ -1064,19 +1078,19 @@ extern "C" double brx_last_timing(brx_ctx *c, int which) {
                                     // state at a later meta-block); 7 = bytes decoded twice (0: every one of those was resumed)
         if (!c->any_launch) return -1.0;
         if (!c->last_counter) return 0.0;
-        uint32_t w[32];
+        uint32_t w[BRX_WC_WORDS];
         if (hipEventSynchronize(c->ev_last) != hipSuccess) return -1.0;
-        if (hipMemcpy(w, c->last_counter, 128, hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
-        if (which == 10) return (double)w[18]; // meta-blocks taken back after a speculative end (the stream read on past its input)
-        if (which == 11) return (double)std::min<uint32_t>(w[19], BRX_LATE2_CAP); // streams level 3 handed on to level 4
-        const uint32_t late = std::min<uint32_t>(w[8], BRX_LATE_CAP);
+        if (hipMemcpy(w, c->last_counter, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
+        if (which == 10) return (double)w[BRX_WC_TAKEN_BACK]; // meta-blocks taken back after a speculative end (the stream read on past its input)
+        if (which == 11) return (double)std::min<uint32_t>(w[BRX_WC_LATE2], BRX_LATE2_CAP); // streams level 3 handed on to level 4
+        const uint32_t late = std::min<uint32_t>(w[BRX_WC_LATE], BRX_LATE_CAP);
         switch (which) {
-        case 2: return (double)w[5] + w[6] + w[7] + late;
-        case 3: return (double)w[6] + w[7];
-        case 4: return (double)w[7];
-        case 5: return (double)w[10];
+        case 2: return (double)w[BRX_WC_LIST] + w[BRX_WC_LIST + 1] + w[BRX_WC_LIST + 2] + late;
+        case 3: return (double)w[BRX_WC_LIST + 1] + w[BRX_WC_LIST + 2];
+        case 4: return (double)w[BRX_WC_LIST + 2];
+        case 5: return (double)w[BRX_WC_LEAN_LISTED];
         case 6: return (double)late;
-        default: return (double)w[11];
+        default: return (double)w[BRX_WC_TWICE];
         }
     }
     if (!c->have_timing) return -1.0;
@@ -1652,8 +1666,11 @@ static int bounded_slice_one(brx_stream *s) {
     HIP_TRY(hipMemcpyAsync(s->d_meta, meta, sizeof meta, hipMemcpyHostToDevice, c->stream));
     const uint64_t pz[4] = {s->sl_pause_at, s->in_slide_pending, s->sl_in_low, s->no_mb_room ? 1ull : 0ull}; // (need_room on the way in: 1 = no pause in front of whole meta-blocks)
     HIP_TRY(hipMemcpyAsync((uint8_t *)s->d_rec + offsetof(BrxResume, pause_at), pz, 32, hipMemcpyHostToDevice, c->stream));
-    int rc = launch(c, c->stream, false, s->d_inwin, s->d_meta, 1, virt, s->d_meta + 2, s->d_meta + 4,
-                    (int32_t *)(s->d_meta + 5), nullptr, s->d_rec, s->d_pool);
+    LaunchReq r;
+    r.in = s->d_inwin; r.in_off = s->d_meta; r.n = 1;
+    r.out = virt; r.out_off = s->d_meta + 2; r.out_len = s->d_meta + 4; r.status = (int32_t *)(s->d_meta + 5);
+    r.resume = s->d_rec; r.own_pool = s->d_pool;
+    int rc = launch(c, c->stream, r);
     if (rc) return rc;
     c->reader_launches++;
     c->reader_slices++;
@@ -1724,8 +1741,10 @@ static int round_launch(brx_ctx *c, const std::vector<brx_stream *> &b) {
     HIP_TRY(hipEventRecord(c->ev_prep, c->stream)); // (the owners' slides and refills of these streams went to the context's stream)
     HIP_TRY(hipStreamWaitEvent(c->s_round, c->ev_prep, 0));
     HIP_TRY(hipMemcpyAsync(c->d_rdesc, c->h_rdesc, (size_t)n * sizeof(BrxReaderDesc), hipMemcpyHostToDevice, c->s_round));
-    int rc = launch(c, c->s_round, false, nullptr, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                    false, 0xffffffffu, c->d_rdesc);
+    LaunchReq r;
+    r.n = n;
+    r.desc = c->d_rdesc;
+    int rc = launch(c, c->s_round, r);
     if (rc) return rc;
     c->reader_launches++;
     c->reader_slices += n;

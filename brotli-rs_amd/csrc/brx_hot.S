@@ -41,32 +41,20 @@
 // for all literal block types, every distance symbol fits its payload form, input < 2^28 bytes, pos + MLEN <= capacity.
 // tools/asm_emu.py runs this file instruction by instruction against LDS states dumped on the GPU and the oracle.
 
-// -DLDS_GROW=bytes: the wider instances of the kernel (brx_kernels_l1/l2/l3.hip, BRX_LDS_GROW of brx_device.h) -- that much
-// more table memory, everything behind it that much further up
-#ifndef LDS_GROW
-#define LDS_GROW 0
-#endif
+// Where the areas of the wave's LDS lie: brx_layout.h, selected by -DBRX_LEVEL=k (the wider instances of the kernel have more
+// table memory and everything behind it that much further up; level 4 has the table memory LAST, so that the fixed areas stay
+// within a DS instruction's 16-bit offset).  The code-length scratch area (Lds::lens) is free during the command loop: the loop
+// keeps ITAB, SPARE and CMH in it.
+#include "brx_layout.h"
 #define RMASK 2047
-#define RING 2048
-#ifdef LDS_TM_LAST
-// level 4 (150 KiB of LDS): the table memory LAST -- the fixed areas stay within a DS instruction's 16-bit offset
-#define LDS_ITAB 2048
-#define LDS_SPARE 2304
-#define LDS_CMH 2560
-#define LDS_ST 2816
-#define LDS_MBW 3008
-#define LDS_PAD0 3200
-#define LDS_TM 3328
-#else
-#define LDS_TM 2048
-#define LDS_ST (9728+LDS_GROW)
-#define LDS_MBW (9920+LDS_GROW)
-// the code-length scratch area (Lds::lens, 768 B) is free during the command loop
-#define LDS_ITAB (8960+LDS_GROW)   // byte -> context info (filled by prepare_fast_tables)
-#define LDS_SPARE (9216+LDS_GROW)  // 12 x 4 B: the two-entry symbol lists of resident one-symbol literal trees
-#define LDS_CMH (9472+LDS_GROW)    // context id * 4 -> tree descriptor of the current literal block type (filled at entry)
-#define LDS_PAD0 (10112+LDS_GROW)
-#endif
+#define RING BRX_L_RING_BYTES
+#define LDS_TM BRX_L_TM
+#define LDS_ST BRX_L_ST
+#define LDS_MBW BRX_L_MBW
+#define LDS_ITAB BRX_L_ITAB
+#define LDS_SPARE BRX_L_SPARE
+#define LDS_CMH BRX_L_CMH
+#define LDS_PAD0 BRX_L_PAD
 #define SYMOFF 68       // symbol list of a tree: after its 17 header words (brx_kernels.hip, "Table layout in table memory")
 #define INFOOFF 64      // the header's info word: kind | max_len << 8 | x << 16
 // EXEC inside the loop: lanes 0..16 only (the 16 comparator lanes of a lookup, + 1).  Everything uniform needs one lane; copies,

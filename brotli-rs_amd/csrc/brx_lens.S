@@ -16,6 +16,8 @@
 //           13 alphabet  14 w_end  15 last dword  16 its mask  17 in_words (SGPR pair)  18 cltab (VGPR)  19 lane id (VGPR)
 // status: 0 = the lengths are complete (alphabet full, or the code space used up), else the reference's error
 // (1 = CodeLengthsChecksum, 18 = ParseErrorComplexPrefixCodeLengths).  The caller stores the last chunk (VCUR, dirty) itself.
+#include "brx_layout.h"
+#define LDS_LENS BRX_L_LENS // Lds::lens of the instance (-DBRX_LEVEL=k / -DBRX_SMALL)
 #define WIN s[60:61]
 #define WINLO s60
 #define NAV s62

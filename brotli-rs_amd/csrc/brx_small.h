@@ -304,7 +304,7 @@ FI u32 sm_stream(Dec &d, Lds &s, const uint4 *__restrict__ iac, const WaveConsts
 __global__ __launch_bounds__(BRX_WAVE, 8) void brx_decode_kernel_s(BrxKernelArgs a) {
     Lds &s = g_lds;
     const u32 lane = threadIdx.x;
-    u32 *const listed = a.work_counter + 10;
+    u32 *const listed = a.work_counter + BRX_WC_LEAN_LISTED;
     // Classification (device-pointer path): the first ceil(n / 64) waves list the streams that are NOT for this kernel, 64
     // per atomic, in index order within a wave.
     if (a.classify != 0u) {
@@ -330,9 +330,9 @@ __global__ __launch_bounds__(BRX_WAVE, 8) void brx_decode_kernel_s(BrxKernelArgs
                     umin = max(umin, (u32)__shfl_xor((int)umin, (int)o));
                 }
                 if (lane == 0u) {
-                    (void)atomicAdd(a.work_counter + 15, units);
-                    (void)atomicMax(a.work_counter + 16, umax);
-                    (void)atomicMax(a.work_counter + 17, umin);
+                    (void)atomicAdd(a.work_counter + BRX_WC_LEAN_UNITS, units);
+                    (void)atomicMax(a.work_counter + BRX_WC_UNITS_MAX, umax);
+                    (void)atomicMax(a.work_counter + BRX_WC_UNITS_MIN, umin);
                 }
             }
         }

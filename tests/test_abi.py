@@ -107,14 +107,14 @@ def test_assembly_loop_passes_the_wait_state_lint():
     import sys
     # both builds of the loop, then the build-time switches kept for A/B and bring-up (serial symbol fetch; in-loop timers):
     # they have their own copies of the lookups / the literal dispatch and must keep assembling
-    for defs in ("", "BRX_WIN_SGPR", "BRX_NO_SPEC", "BRX_NO_SPEC BRX_WIN_SGPR", "BRX_PROF", "LDS_TM_LAST BRX_WIN_SGPR"):  # (the last one: level 4's layout)
+    for defs in ("", "BRX_WIN_SGPR", "BRX_NO_SPEC", "BRX_NO_SPEC BRX_WIN_SGPR", "BRX_PROF", "BRX_LEVEL=4 BRX_WIN_SGPR"):  # (the last one: level 4's layout)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "asm_hazard_lint.py")], capture_output=True, text=True,
                            env=dict(os.environ, ASM_DEFS=defs))
         assert r.returncode == 0, r.stdout + r.stderr
         assert "0 finding(s)" in r.stdout
     # the code-length symbol loop of the header path (an asm statement with operands: stand-in registers for the lint)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "asm_hazard_lint.py"), os.path.join(ROOT, "brotli-rs_amd", "csrc", "brx_lens.S")],
-                       capture_output=True, text=True, env=dict(os.environ, ASM_DEFS="LDS_LENS=8960"))
+                       capture_output=True, text=True, env=dict(os.environ, ASM_DEFS="BRX_LEVEL=0"))
     assert r.returncode == 0 and "0 finding(s)" in r.stdout, r.stdout + r.stderr
 
 

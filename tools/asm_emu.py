@@ -29,8 +29,16 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang"
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 U32 = np.uint32
 MASK32 = 0xFFFFFFFF
-LDS_BYTES = 10240
-RING_BYTES = 2048  # BRX_RING_BYTES
+
+
+def layout(*names):
+    """Values of brx_layout.h macros for level 0, the layout of the dumps: the preprocessor expands them, Python adds them up."""
+    src = '#include "brx_layout.h"\n' + "\n".join(names) + "\n"
+    out = subprocess.check_output(["cpp", "-P", "-I", os.path.join(ROOT, "brotli-rs_amd", "csrc"), "-"], input=src.encode()).decode()
+    return [int(eval(line, {"__builtins__": {}})) for line in out.splitlines() if line.strip()]
+
+
+LDS_BYTES, RING_BYTES, ST, MBW = layout("BRX_L_BYTES", "BRX_L_RING_BYTES", "BRX_L_ST", "BRX_L_MBW")
 DUMP_WORDS = 16 + LDS_BYTES // 4
 S_VCC, S_M0, S_EXEC = 106, 124, 126
 
@@ -806,9 +814,6 @@ def oracle_trace(stream):
         if line.startswith("CMDX "):
             cmds.append([int(x) for x in line.split()[1:]])
     return r.stdout, cmds
-
-
-ST, MBW = 9728, 9920
 
 
 def lds_u32(lds, off):
