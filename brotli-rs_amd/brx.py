@@ -4,6 +4,7 @@ item, `brotli::Decompressor<R: Read>` (reference src/lib.rs:377-410, 2173-2193).
 Plumbing only: every decode goes through the C ABI into the gfx950 kernels.  If the library or a GPU is
 missing this module FAILS LOUDLY (BrxError); there is no CPU fallback anywhere in the product path.
 """
+import contextlib
 import ctypes
 import io
 import os
@@ -77,6 +78,9 @@ def load_library():
     L.brx_digest_batch.restype = ctypes.c_int
     L.brx_digest_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.brx_index_batch.restype = ctypes.c_int
+    L.brx_index_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -132,7 +136,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_host_alloc", "brx_host_free", "brx_stream_new_bounded", "brx_generate_batch", "brx_compact_batch",
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
-                    "brx_stream_advance", "brx_stream_ready", "brx_digest_batch"]
+                    "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch"]
 
 
 def status_str(code: int) -> str:
@@ -293,6 +297,40 @@ class Context:
         if expect is not None:
             return digest[:n], mismatch[:n]
         return digest[:n]
+
+    def index_batch_device(self, delim, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr=None, pos_ptr=None, total=0,
+                           hip_stream=None):
+        """brx_index_batch on raw device pointers: count[i] = bytes equal to `delim` in out[out_off[i] .. + len[i]); with pos_off / pos
+        also pos[pos_off[i] + k] = offset within stream i of the k-th of them (entries at or beyond `total` are not written)."""
+        rc = self._lib.brx_index_batch(self._h, delim, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, total,
+                                       hip_stream)
+        if rc != 0:
+            raise BrxError("brx_index_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def index_batch(self, out, out_off, out_len, delim=10, stream=None, positions=True):
+        """Record boundaries of the decoded streams of a batch, on the device.  out: uint8 device tensor (the whole arena); out_off:
+        int64 device tensor, the first len(out_len) entries are used; out_len: int64 device tensor, the entries of failed streams
+        zeroed; delim: the delimiter byte (default newline).  Returns (count, pos_off, pos), int64 device tensors: count[i] delimiters
+        in stream i, pos[pos_off[i] + k] the offset within stream i of the k-th -- or `count` alone with positions=False.  stream: a
+        torch.cuda.Stream the work is enqueued on; None = the context's own stream.  With positions the call reads the grand total
+        back to allocate `pos`: the one synchronisation a caller that wants the positions cannot avoid."""
+        import torch
+        n = int(out_len.numel())
+        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass clears it itself)
+        hs = stream.cuda_stream if stream is not None else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        args = (int(delim), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
+        self.index_batch_device(*args, count.data_ptr(), hip_stream=hs)
+        if not positions:
+            return count
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ends = torch.cumsum(count, 0)
+            pos_off = ends - count
+            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
+            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
+        self.index_batch_device(*args, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
+        return count, pos_off, pos[:total]
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

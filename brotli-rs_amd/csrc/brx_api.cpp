@@ -29,6 +29,7 @@
 #include "_gen/brx_tables_gen.h" // BRX_DICT, BRX_CONTEXT_LUT, BRX_TRANSFORMS  (tools/bin2h.py from tables/*.bin)
 #include "brx_device.h"
 #include "brx_digest.h"
+#include "brx_index.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -67,6 +68,7 @@ static int fail(int code, const char *what, hipError_t e = hipSuccess) {
     }
 
 #define BRX_COUNTER_RING 64u   // launches in flight on one context before a work counter is reused
+#define BRX_INDEX_RING 16u    // the same for brx_index_batch
 #define BRX_DIGEST_RING 16u   // brx_digest_batch launches in flight on one context before a scratch region is reused (the call then waits)
 #define BRX_MAX_CHUNKS 8u      // host-pointer pipeline: H2D / decode / D2H chunks in flight
 #define BRX_STREAM_LIMIT 0xffffff00ull // per-stream output limit of the 32-bit position arithmetic
@@ -179,6 +181,13 @@ struct brx_ctx {
     uint64_t digest_seq = 0;
     hipEvent_t ev_digest[BRX_DIGEST_RING] = {};   // recorded behind the launch that used the region
     bool digest_used[BRX_DIGEST_RING] = {};
+    // brx_index_batch (brx_index.hip): scratch of BRX_INDEX_RING launches (ticket counters, tile prefix sums, per-tile counts), every
+    // launch in a region of its own
+    uint8_t *d_index_scratch = nullptr;
+    size_t index_cap_n = 0, index_cap_tiles = 0;  // streams / tiles one region holds
+    uint64_t index_seq = 0;
+    hipEvent_t ev_index[BRX_INDEX_RING] = {};     // recorded behind the launch that used the region
+    bool index_used[BRX_INDEX_RING] = {};
     std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
     std::vector<uint8_t *> stage_free;
     size_t stage_bytes = 0;
@@ -265,6 +274,9 @@ static void ctx_release(brx_ctx *c) {
     for (auto &t : c->d_digest_tab) (void)hipFree(t);
     (void)hipFree(c->d_digest_scratch);
     for (auto &ev : c->ev_digest)
+        if (ev) (void)hipEventDestroy(ev);
+    (void)hipFree(c->d_index_scratch);
+    for (auto &ev : c->ev_index)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -1287,6 +1299,57 @@ extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, c
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ev_digest[slot], st));
         c->digest_used[slot] = true;
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- record boundaries of the decoded streams of a batch (brx_index.hip) ----------------------------------------------------
+void brx_launch_index(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint8_t delim,
+                      void *scratch, uint64_t max_tiles, uint64_t *count, const uint64_t *pos_off, uint64_t *pos, uint64_t total,
+                      unsigned workgroups, void *hip_stream);
+
+extern "C" int brx_index_batch(brx_ctx *c, uint8_t delim, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                               uint64_t span, uint64_t *count, const uint64_t *pos_off, uint64_t *pos, uint64_t total,
+                               void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: ctx is NULL");
+    if ((pos_off == nullptr) != (pos == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: pos_off and pos go together");
+    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: count is NULL in count mode");
+    if (n == 0) return BRX_SUCCESS;
+    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: NULL table");
+    // what the scratch of a launch must hold follows from n and span alone: no length is read back
+    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
+    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: span out of range");
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        if (n > c->index_cap_n || max_tiles > c->index_cap_tiles || !c->d_index_scratch) {
+            // (rare) a larger scratch: launches on any stream may still use the old one
+            HIP_TRY(hipDeviceSynchronize());
+            for (auto &u : c->index_used) u = false;
+            (void)hipFree(c->d_index_scratch);
+            c->d_index_scratch = nullptr;
+            const size_t cap_n = std::max(c->index_cap_n, (size_t)n + n / 4u + 1024u);
+            const size_t cap_tiles = std::max(c->index_cap_tiles, (size_t)(max_tiles + max_tiles / 4u + 1024u));
+            c->index_cap_n = c->index_cap_tiles = 0;
+            hipError_t e = hipMalloc(&c->d_index_scratch, brx_ix_region_bytes(cap_n, cap_tiles) * BRX_INDEX_RING);
+            if (e != hipSuccess) return fail(BRX_ERR_OUT_OF_MEMORY, "index scratch allocation failed", e);
+            c->index_cap_n = cap_n;
+            c->index_cap_tiles = cap_tiles;
+        }
+        const unsigned slot = (unsigned)(c->index_seq++ % BRX_INDEX_RING);
+        if (!c->ev_index[slot]) HIP_TRY(hipEventCreateWithFlags(&c->ev_index[slot], hipEventDisableTiming));
+        if (c->index_used[slot]) HIP_TRY(hipEventSynchronize(c->ev_index[slot])); // the launch that had this region 16 calls ago
+        void *scratch = c->d_index_scratch + brx_ix_region_bytes(c->index_cap_n, c->index_cap_tiles) * slot;
+        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+        brx_launch_index(out, out_off, len, n, span, delim, scratch, max_tiles, count, pos_off, pos, total, c->max_grid / 4u, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->ev_index[slot], st));
+        c->index_used[slot] = true;
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;

@@ -157,7 +157,7 @@ template <class D> size_t advance(D *const *ds, size_t n) {
 }
 template <class D> size_t advance(const std::vector<D *> &ds) { return advance(ds.data(), ds.size()); }
 
-// The two device-memory passes over a decoded batch (BRX_MEM_DEVICE; every pointer is device memory, `stream` a hipStream_t or
+// The device-memory passes over a decoded batch (BRX_MEM_DEVICE; every pointer is device memory, `stream` a hipStream_t or
 // nullptr for the context's own): the decoded bytes back to back, and their CRC-32 / CRC-32C (kind = BRX_DIGEST_*; `expect` and
 // `mismatch` both or neither) -- a batch that never leaves the device is verified there.  brx.h has the contracts.
 inline void compact_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint8_t *dst,
@@ -169,6 +169,14 @@ inline void digest_batch(brx_ctx *ctx, uint32_t kind, const uint8_t *out, const 
                          uint32_t *digest, const uint32_t *expect = nullptr, uint32_t *mismatch = nullptr, void *stream = nullptr) {
     if (brx_digest_batch(ctx, kind, out, out_off, len, n, digest, expect, mismatch, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_digest_batch: ") + brx_last_error());
+}
+// Record boundaries of the same batch: count[i] = bytes equal to `delim` in stream i; with `pos_off` (the exclusive prefix sum of the
+// counts) and `pos` (room for `total` entries) also their offsets within the stream, ascending.  `span` = size of the arena behind `out`.
+inline void index_batch(brx_ctx *ctx, uint8_t delim, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                        uint64_t span, uint64_t *count, const uint64_t *pos_off = nullptr, uint64_t *pos = nullptr, uint64_t total = 0,
+                        void *stream = nullptr) {
+    if (brx_index_batch(ctx, delim, out, out_off, len, n, span, count, pos_off, pos, total, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_index_batch: ") + brx_last_error());
 }
 
 } // namespace brotli

@@ -293,6 +293,40 @@ int brx_compact_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off,
 int brx_digest_batch(brx_ctx *ctx, uint32_t kind, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
                      uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, void *hip_stream);
 
+/* ---- record boundaries of the decoded bytes of a batch (device memory only) -------------------------------
+ * Nearly everything that is decoded is delimited text, and the first thing a consumer on the device (a tokenizer, a parser, a data
+ * loader) does with a batch is find where its records start.  This pass knows the slot layout and does it at memory rate:
+ *   count[i]              = number of bytes equal to `delim` in out[out_off[i] .. out_off[i] + len[i])          for i < n
+ *   pos[pos_off[i] + k]   = offset WITHIN stream i of its k-th such byte, ascending in k                          (fill mode)
+ * out, out_off, len and n are exactly as for brx_compact_batch and brx_digest_batch: `len` is brx_decode_batch's out_len with the
+ * entries of failed streams zeroed, out_off needs no alignment, bytes of a slot beyond len[i] never enter a result.  All pointers
+ * are DEVICE memory.
+ *   span      the size in bytes of the arena `out` points into.  The caller guarantees out_off[i] + len[i] <= span and that slots do
+ *             not overlap.  The host uses it for one thing: to bound the work items (at most span / 65536 + 2 n tiles of 64 KiB), so
+ *             that scratch is sized without a length read back.  Nothing at or beyond out + span (or in front of out) is ever
+ *             loaded; a batch with more tiles than `span` allows has the surplus ignored, never written out of bounds.
+ *   count mode (pos_off == NULL and pos == NULL; count required): count[i] as above, n entries.
+ *   fill mode  (pos_off and pos both given; count may be NULL, and if given it is written as in count mode): pos_off is the exclusive
+ *             prefix sum of the counts (n entries, computed by the caller, e.g. torch.cumsum -- the convention of dst_off of
+ *             brx_compact_batch) and `total` the number of entries pos has room for: an entry whose index is >= total is not
+ *             written, so a caller whose counts went stale corrupts nothing.
+ * Record k of stream i is the bytes [pos[k-1] + 1, pos[k]] of the stream (from 0 for k = 0), its delimiter included; a trailing
+ * record without a delimiter runs from behind the last position to len[i].
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued (behind a
+ * brx_decode_batch on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.
+ * Scratch (tile prefix sums, per-tile counts, two ticket counters) belongs to the context and is sized from n and span; every
+ * launch has a region of its own, so calls on different HIP streams of one context may overlap; a call with a larger n or span than
+ * any before synchronises the device once to grow it, and the 17th call in flight waits on the host for the first.
+ * BRX_ERR_INVALID_ARGUMENT: ctx NULL, out_off or len NULL with n > 0, only one of pos_off / pos, count NULL in count mode.
+ * n = 0 returns BRX_SUCCESS, no launch.  Count mode is one pass over the bytes (reads sum(len), writes 8 n), fill mode two (the
+ * second mostly from cache) plus 8 bytes per delimiter; no reference counterpart. */
+int brx_index_batch(brx_ctx *ctx, uint8_t delim,
+                    const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                    uint64_t span,
+                    uint64_t *count,
+                    const uint64_t *pos_off, uint64_t *pos, uint64_t total,
+                    void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one

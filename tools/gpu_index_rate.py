@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Times brx_index_batch (record boundaries of a decoded batch, on the device) with HIP events, in one run on one batch:
+
+  headline  the decoded output of N x alice29 (default 4096) in device memory, delim = '\\n': count mode, fill mode (pos_off from a
+            count-mode call and torch.cumsum, outside the timed window), brx_compact_batch over the same slots (the yardstick for ONE
+            pass over this ragged layout; it also writes what it reads) and brx_digest_batch (CRC-32) over the same slots
+  large     fill mode over one stream of 70 MiB (random bytes: one delimiter in 256)
+  ragged    fill mode over 4096 streams, lengths log-uniform over 1 B .. 4 MiB (fixed seed, random bytes)
+
+Every timed call is warmed up first, timed `--reps` times in windows of `--inner` back-to-back calls between two events; the median
+and the spread of the per-call times are printed.  Counts and positions are checked against numpy on the host (not in the timed
+window).  Usage: python tools/gpu_index_rate.py [--n 4096] [--reps 9] [--inner 100] [--out FILE]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from brotli_rs_amd import brx  # noqa: E402
+import brx_knobs  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--n", type=int, default=4096)
+ap.add_argument("--reps", type=int, default=9)
+ap.add_argument("--inner", type=int, default=100)
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+
+dev = torch.device("cuda", 0)
+ctx = brx_knobs.context(0)
+stream = torch.cuda.Stream(device=dev)
+lines = []
+NL = 10
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def timed(fn):
+    """fn() enqueues one call on `stream`.  -> (median, min, max) milliseconds per call."""
+    for _ in range(3):
+        fn()
+    stream.synchronize()
+    per = []
+    for _ in range(args.reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        for _ in range(args.inner):
+            fn()
+        b.record(stream)
+        b.synchronize()
+        per.append(a.elapsed_time(b) / args.inner)
+    per.sort()
+    return per[len(per) // 2], per[0], per[-1]
+
+
+def index_rates(name, arena, offs, lens, reference, count_mode=True):
+    """Count mode (if asked) and fill mode over one batch; reference(i) -> np positions of stream i (checked on a sample).
+    -> {mode: median ms}"""
+    n = lens.numel()
+    total_bytes = int(lens.sum().item())
+    base = (arena.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, arena.numel())
+    count = torch.zeros(n, dtype=torch.int64, device=dev)
+    res = {}
+
+    def count_call():
+        ctx.index_batch_device(NL, *base, count.data_ptr(), hip_stream=stream.cuda_stream)
+    count_call()
+    stream.synchronize()
+    if count_mode:
+        res["count"] = timed(count_call)
+    pos_off = torch.cumsum(count, 0) - count
+    entries = int(count.sum().item())
+    pos = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+
+    def fill_call():
+        ctx.index_batch_device(NL, *base, None, pos_off.data_ptr(), pos.data_ptr(), entries, hip_stream=stream.cuda_stream)
+    res["fill"] = timed(fill_call)
+    h_count, h_off, h_pos = count.cpu().numpy(), pos_off.cpu().numpy(), pos.cpu().numpy()
+    for i in sorted(set(np.linspace(0, n - 1, 16).astype(int).tolist())):
+        want = reference(i)
+        assert h_count[i] == want.size, "%s: count of stream %d differs from numpy" % (name, i)
+        assert (h_pos[h_off[i]:h_off[i] + h_count[i]] == want).all(), "%s: positions of stream %d differ from numpy" % (name, i)
+    for mode, (med, lo, hi) in res.items():
+        say("%-9s index %-6s  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s   [%d streams, %.1f MB, %d delimiters]"
+            % (name, mode, med, lo, hi, total_bytes / med / 1e6, n, total_bytes / 1e6, entries))
+    return {m: v[0] for m, v in res.items()}
+
+
+# ---- headline: N x alice29, decoded on the device -------------------------------------------------------------------------
+n = args.n
+comp = open(os.path.join(ROOT, "tests", "golden", "data", "alice29.txt.compressed"), "rb").read()
+text = open(os.path.join(ROOT, "tests", "golden", "data", "alice29.txt"), "rb").read()
+cap = (len(text) + 15) & ~15
+blob = torch.frombuffer(bytearray(comp), dtype=torch.uint8).to(dev).repeat(n).contiguous()
+in_off = torch.arange(n + 1, dtype=torch.int64, device=dev) * len(comp)
+out_off = torch.arange(n + 1, dtype=torch.int64, device=dev) * cap
+out = torch.zeros(n * cap, dtype=torch.uint8, device=dev)
+out_len = torch.zeros(n, dtype=torch.int64, device=dev)
+status = torch.full((n,), -1, dtype=torch.int32, device=dev)
+torch.cuda.synchronize()
+ctx.decode_batch_device(blob.data_ptr(), in_off.data_ptr(), n, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), status.data_ptr())
+ctx.synchronize()
+assert not status.any().item() and (out_len == len(text)).all().item()
+say("headline  %d x alice29 decoded on the device: %.1f MB in slots of %d bytes" % (n, n * len(text) / 1e6, cap))
+
+dst = torch.zeros(n * len(text), dtype=torch.uint8, device=dev)
+dst_off = torch.arange(n, dtype=torch.int64, device=dev) * len(text)
+
+
+def compact():
+    ctx.compact_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, dst.data_ptr(), dst_off.data_ptr(),
+                             n * len(text), hip_stream=stream.cuda_stream)
+
+
+compact_ms, lo, hi = timed(compact)
+say("headline  compact       %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s read + as much written" % (compact_ms, lo, hi, n * len(text) / compact_ms / 1e6))
+digest = torch.zeros(n, dtype=torch.int32, device=dev)
+
+
+def digest_call():
+    ctx.digest_batch_device(brx.DIGEST_KINDS["crc32"], out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, digest.data_ptr(),
+                            hip_stream=stream.cuda_stream)
+
+
+digest_ms, lo, hi = timed(digest_call)
+say("headline  digest crc32  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s" % (digest_ms, lo, hi, n * len(text) / digest_ms / 1e6))
+want_text = np.flatnonzero(np.frombuffer(text, dtype=np.uint8) == NL)
+res = index_rates("headline", out, out_off, out_len, lambda i: want_text)
+for mode, ms in res.items():
+    say("headline  index %-6s = %.3f x compact, %.3f x digest" % (mode, ms / compact_ms, ms / digest_ms))
+del blob, dst
+
+# ---- one large stream ------------------------------------------------------------------------------------------------
+g = torch.Generator(device=dev)
+g.manual_seed(7)
+big_n = (70 << 20) + 12345
+arena = torch.randint(0, 256, (big_n + 64,), dtype=torch.uint8, device=dev, generator=g)
+host = arena.cpu().numpy()
+index_rates("large", arena, torch.tensor([3], dtype=torch.int64, device=dev), torch.tensor([big_n], dtype=torch.int64, device=dev),
+            lambda i: np.flatnonzero(host[3:3 + big_n] == NL), count_mode=False)
+
+# ---- 4096 log-uniform lengths -------------------------------------------------------------------------------------------
+rng = np.random.default_rng(1234)
+top = 4 << 20
+h_lens = np.clip(np.floor(np.exp(rng.uniform(0.0, np.log(top), 4096))).astype(np.int64), 1, top)
+slots = h_lens + rng.integers(0, 64, 4096)
+h_offs = np.zeros(4096, dtype=np.int64)
+np.cumsum(slots[:-1], out=h_offs[1:])
+g.manual_seed(99)
+arena = torch.randint(0, 256, (int(h_offs[-1] + slots[-1]),), dtype=torch.uint8, device=dev, generator=g)
+host = arena.cpu().numpy()
+index_rates("ragged", arena, torch.from_numpy(h_offs).to(dev), torch.from_numpy(h_lens).to(dev),
+            lambda i: np.flatnonzero(host[h_offs[i]:h_offs[i] + h_lens[i]] == NL), count_mode=False)
+ctx.close()
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
