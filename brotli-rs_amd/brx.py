@@ -381,6 +381,10 @@ class Context:
         """(batches, streams) the Read facade has launched for queued streams on this context (brx_last_timing 14 / 15)."""
         return int(self._lib.brx_last_timing(self._h, 14)), int(self._lib.brx_last_timing(self._h, 15))
 
+    def facade_streams(self):
+        """Streams in those batches, a stream queued again after status 25 counted every time (brx_last_timing 15)."""
+        return int(self._lib.brx_last_timing(self._h, 15))
+
     def stream_regrown(self):
         """Slices of bounded / pulled streams of this context run again with a larger output buffer (one command beyond the slack)."""
         return int(self._lib.brx_last_timing(self._h, 9))

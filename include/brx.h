@@ -53,7 +53,10 @@ enum {
     BRX_RING_BUFFER_ERROR = 22,
     BRX_RUN_LENGTH_EXCEEDED_SIZE_OF_CONTEXT_MAP = 23,
     BRX_UNEXPECTED_EOF = 24,
-    BRX_OUTPUT_TOO_SMALL = 25, /* capacity out_off[i+1]-out_off[i] exhausted; out_len[i] = bytes needed so far */
+    BRX_OUTPUT_TOO_SMALL = 25, /* capacity out_off[i+1]-out_off[i] exhausted; out_len[i] = bytes needed so far: the position in front of
+                                  the item that did not fit plus that item's size (an insert's literals, a copy, a dictionary word, an
+                                  uncompressed meta-block); no byte outside the slot is written for any status, the slot's own bytes are
+                                  unspecified under this one */
     BRX_REF_PANIC = 26,        /* the reference would panic here: UppercaseFirst on a dictionary word that
                                   starts with 0x00 (src/transformation/mod.rs:52-82) */
     BRX_INTERNAL_WATCHDOG = 27 /* bug guard inside the kernel.  Unreachable from any stream the reference terminates on, by construction:

@@ -71,6 +71,16 @@ def decode(data: bytes, flags: int = 0, cap: int = None, want_stats: bool = Fals
         return (rc, out, st.as_dict()) if want_stats else (rc, out)
 
 
+def decode_at(data: bytes, cap: int, flags: int = 0):
+    """Decode one stream into exactly `cap` bytes.  Returns (status, out_len, bytes) with out_len unclipped: the decoded size
+    for status 0, the bytes needed so far for status 25, the position reached for any other status.  bytes: the slot's first
+    min(out_len, cap) bytes (for status 25 the whole slot, zeros behind what was decoded)."""
+    buf = ctypes.create_string_buffer(max(cap, 1))
+    n = ctypes.c_size_t(0)
+    rc = lib().bro_decode(data, len(data), buf, cap, ctypes.byref(n), flags, None)
+    return rc, int(n.value), buf.raw[:min(n.value, cap)]
+
+
 def status_str(code: int) -> str:
     return lib().bro_status_str(code).decode("utf-8")
 

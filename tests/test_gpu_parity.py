@@ -102,6 +102,8 @@ def test_output_too_small(ctx):
     outs, status, out_len = ctx.decode_batch([_read("alice29.txt.compressed")], [1000])
     assert status[0] == 25
     assert 1000 < int(out_len[0]) <= 152089
+    want = oracle.decode_at(_read("alice29.txt.compressed"), 1000)
+    assert want[0] == 25 and int(out_len[0]) == want[1]  # the position in front of the item that did not fit + that item's size
 
 
 def test_replicated_batch_matches_oracle(ctx):
@@ -1098,8 +1100,9 @@ def test_wide_kernel_takes_the_streams_whose_tables_spill(ctx):
     assert all(int(st) == 0 for st in status) and all(o == _read("alice29.txt") for o in outs)
     # a spilling stream whose slot is too small: status 25 and the length needed so far, from whichever kernel meets it
     outs, status, out_len = ctx.decode_batch([lcet, alice, lcet], [1000, 200000, 500000])
-    w0 = oracle.decode(lcet, 0, cap=1000)
+    w0 = oracle.decode_at(lcet, 1000)
     assert [int(x) for x in status] == [25, 0, 0] and w0[0] == 25 and len(lcet_out) > 1000
+    assert int(out_len[0]) == w0[1] > 1000
     assert outs[2] == lcet_out
 
 
