@@ -68,12 +68,58 @@ static int fail(int code, const char *what, hipError_t e = hipSuccess) {
     }
 
 #define BRX_COUNTER_RING 64u   // launches in flight on one context before a work counter is reused
-#define BRX_INDEX_RING 16u    // the same for brx_index_batch
-#define BRX_DIGEST_RING 16u   // brx_digest_batch launches in flight on one context before a scratch region is reused (the call then waits)
+#define BRX_PASS_RING 16u      // launches of one tile pass in flight on one context before a scratch region is reused (the call then waits)
 #define BRX_MAX_CHUNKS 8u      // host-pointer pipeline: H2D / decode / D2H chunks in flight
 #define BRX_STREAM_LIMIT 0xffffff00ull // per-stream output limit of the 32-bit position arithmetic
 
 struct brx_stream;
+
+// Scratch of a tile pass (brx_tiles.h): BRX_PASS_RING regions, every launch in one of its own, taken in turn (under brx_ctx::mu).
+struct PassRing {
+    uint8_t *base = nullptr;
+    size_t region_bytes = 0;
+    uint64_t seq = 0;
+    hipEvent_t ev[BRX_PASS_RING] = {};            // recorded behind the launch that used the region
+    bool used[BRX_PASS_RING] = {};
+};
+
+// Make sure a region holds `bytes`; if it does not, the regions become `grow` bytes (>= bytes) each and never smaller than they were.
+static int ring_reserve(PassRing &r, size_t bytes, size_t grow, const char *oom) {
+    if (r.base && bytes <= r.region_bytes) return BRX_SUCCESS;
+    // (rare) a larger scratch: launches on any stream may still use the old one
+    HIP_TRY(hipDeviceSynchronize());
+    for (auto &u : r.used) u = false;
+    (void)hipFree(r.base);
+    r.base = nullptr;
+    const size_t region = std::max(r.region_bytes, grow);
+    hipError_t e = hipMalloc(&r.base, region * BRX_PASS_RING);
+    if (e != hipSuccess) return fail(BRX_ERR_OUT_OF_MEMORY, oom, e);
+    r.region_bytes = region;
+    return BRX_SUCCESS;
+}
+
+// The next region in turn -> *scratch; waits on the host while the launch that had it BRX_PASS_RING calls ago is in flight.
+static int ring_take(PassRing &r, void **scratch) {
+    const unsigned slot = (unsigned)(r.seq++ % BRX_PASS_RING);
+    if (!r.ev[slot]) HIP_TRY(hipEventCreateWithFlags(&r.ev[slot], hipEventDisableTiming));
+    if (r.used[slot]) HIP_TRY(hipEventSynchronize(r.ev[slot]));
+    *scratch = r.base + r.region_bytes * slot;
+    return BRX_SUCCESS;
+}
+
+// Behind the launch on `st` that used the region taken last.
+static int ring_record(PassRing &r, hipStream_t st) {
+    const unsigned slot = (unsigned)((r.seq - 1u) % BRX_PASS_RING);
+    HIP_TRY(hipEventRecord(r.ev[slot], st));
+    r.used[slot] = true;
+    return BRX_SUCCESS;
+}
+
+static void ring_free(PassRing &r) {
+    (void)hipFree(r.base);
+    for (auto &ev : r.ev)
+        if (ev) (void)hipEventDestroy(ev);
+}
 
 struct brx_ctx {
     int device = 0;
@@ -173,21 +219,12 @@ struct brx_ctx {
     hipEvent_t ev_prep = nullptr;
     BrxReaderDesc *h_rdesc = nullptr, *d_rdesc = nullptr; // max_grid descriptors: pinned host table, device table
     uint64_t reader_launches = 0, reader_slices = 0; // slice launches of bounded / pulled streams / slices in them (brx_last_timing 16 / 17)
-    // brx_digest_batch (brx_digest.hip): the table block of each kind, built by the host on first use; scratch of BRX_DIGEST_RING
-    // launches (ticket counter, tile prefix sums, per-stream accumulators), every launch in a region of its own
+    // brx_digest_batch (brx_digest.hip): the table block of each kind, built by the host on first use; scratch (ticket counter, tile
+    // prefix sums, per-stream accumulators)
     uint32_t *d_digest_tab[2] = {nullptr, nullptr};
-    uint8_t *d_digest_scratch = nullptr;
-    size_t digest_cap = 0;                        // streams one region holds
-    uint64_t digest_seq = 0;
-    hipEvent_t ev_digest[BRX_DIGEST_RING] = {};   // recorded behind the launch that used the region
-    bool digest_used[BRX_DIGEST_RING] = {};
-    // brx_index_batch (brx_index.hip): scratch of BRX_INDEX_RING launches (ticket counters, tile prefix sums, per-tile counts), every
-    // launch in a region of its own
-    uint8_t *d_index_scratch = nullptr;
-    size_t index_cap_n = 0, index_cap_tiles = 0;  // streams / tiles one region holds
-    uint64_t index_seq = 0;
-    hipEvent_t ev_index[BRX_INDEX_RING] = {};     // recorded behind the launch that used the region
-    bool index_used[BRX_INDEX_RING] = {};
+    PassRing digest_ring;
+    // brx_index_batch (brx_index.hip): scratch (ticket counters, tile prefix sums, per-tile counts)
+    PassRing index_ring;
     std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
     std::vector<uint8_t *> stage_free;
     size_t stage_bytes = 0;
@@ -272,12 +309,8 @@ static void ctx_release(brx_ctx *c) {
     (void)hipFree(c->d_gen_header);
     (void)hipFree(c->st_gen);
     for (auto &t : c->d_digest_tab) (void)hipFree(t);
-    (void)hipFree(c->d_digest_scratch);
-    for (auto &ev : c->ev_digest)
-        if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(c->d_index_scratch);
-    for (auto &ev : c->ev_index)
-        if (ev) (void)hipEventDestroy(ev);
+    ring_free(c->digest_ring);
+    ring_free(c->index_ring);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_in)
@@ -1244,11 +1277,6 @@ extern "C" int brx_compact_batch(brx_ctx *c, const uint8_t *out, const uint64_t 
 }
 
 // ---- CRC-32 / CRC-32C of the decoded streams of a batch (brx_digest.hip) ---------------------------------------------------
-void brx_launch_digest(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, const uint32_t *tab, uint32_t poly,
-                       void *scratch, uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, unsigned workgroups, void *hip_stream);
-
-static size_t digest_region_bytes(size_t cap) { return (128u + (cap + 1u) * 8u + cap * 4u + 127u) & ~(size_t)127u; }
-
 extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
                                 uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, void *hip_stream) {
     BRX_GUARD_BEGIN
@@ -1278,27 +1306,15 @@ extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, c
             }
             tab = d;
         }
-        if (n > c->digest_cap || !c->d_digest_scratch) {
-            // (rare) a larger scratch: launches on any stream may still use the old one
-            HIP_TRY(hipDeviceSynchronize());
-            for (auto &u : c->digest_used) u = false;
-            (void)hipFree(c->d_digest_scratch);
-            c->d_digest_scratch = nullptr;
-            c->digest_cap = 0;
-            const size_t cap = (size_t)n + n / 4u + 1024u;
-            hipError_t e = hipMalloc(&c->d_digest_scratch, digest_region_bytes(cap) * BRX_DIGEST_RING);
-            if (e != hipSuccess) return fail(BRX_ERR_OUT_OF_MEMORY, "digest scratch allocation failed", e);
-            c->digest_cap = cap;
-        }
-        const unsigned slot = (unsigned)(c->digest_seq++ % BRX_DIGEST_RING);
-        if (!c->ev_digest[slot]) HIP_TRY(hipEventCreateWithFlags(&c->ev_digest[slot], hipEventDisableTiming));
-        if (c->digest_used[slot]) HIP_TRY(hipEventSynchronize(c->ev_digest[slot])); // the launch that had this region 16 calls ago
-        void *scratch = c->d_digest_scratch + digest_region_bytes(c->digest_cap) * slot;
+        int rc = ring_reserve(c->digest_ring, brx_dg_region_bytes(n), brx_dg_region_bytes((size_t)n + n / 4u + 1024u),
+                              "digest scratch allocation failed");
+        void *scratch = nullptr;
+        if (rc == BRX_SUCCESS) rc = ring_take(c->digest_ring, &scratch);
+        if (rc != BRX_SUCCESS) return rc;
         // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU, 80 of its 160 KiB of LDS (max_grid = 16 per CU)
         brx_launch_digest(out, out_off, len, n, tab, poly, scratch, digest, expect, mismatch, c->max_grid / 4u, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_digest[slot], st));
-        c->digest_used[slot] = true;
+        if ((rc = ring_record(c->digest_ring, st)) != BRX_SUCCESS) return rc;
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;
@@ -1306,10 +1322,6 @@ extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, c
 }
 
 // ---- record boundaries of the decoded streams of a batch (brx_index.hip) ----------------------------------------------------
-void brx_launch_index(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint8_t delim,
-                      void *scratch, uint64_t max_tiles, uint64_t *count, const uint64_t *pos_off, uint64_t *pos, uint64_t total,
-                      unsigned workgroups, void *hip_stream);
-
 extern "C" int brx_index_batch(brx_ctx *c, uint8_t delim, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
                                uint64_t span, uint64_t *count, const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                                void *hip_stream) {
@@ -1327,29 +1339,16 @@ extern "C" int brx_index_batch(brx_ctx *c, uint8_t delim, const uint8_t *out, co
         std::lock_guard<std::mutex> lk(c->mu);
         HIP_TRY(hipSetDevice(c->device));
         st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        if (n > c->index_cap_n || max_tiles > c->index_cap_tiles || !c->d_index_scratch) {
-            // (rare) a larger scratch: launches on any stream may still use the old one
-            HIP_TRY(hipDeviceSynchronize());
-            for (auto &u : c->index_used) u = false;
-            (void)hipFree(c->d_index_scratch);
-            c->d_index_scratch = nullptr;
-            const size_t cap_n = std::max(c->index_cap_n, (size_t)n + n / 4u + 1024u);
-            const size_t cap_tiles = std::max(c->index_cap_tiles, (size_t)(max_tiles + max_tiles / 4u + 1024u));
-            c->index_cap_n = c->index_cap_tiles = 0;
-            hipError_t e = hipMalloc(&c->d_index_scratch, brx_ix_region_bytes(cap_n, cap_tiles) * BRX_INDEX_RING);
-            if (e != hipSuccess) return fail(BRX_ERR_OUT_OF_MEMORY, "index scratch allocation failed", e);
-            c->index_cap_n = cap_n;
-            c->index_cap_tiles = cap_tiles;
-        }
-        const unsigned slot = (unsigned)(c->index_seq++ % BRX_INDEX_RING);
-        if (!c->ev_index[slot]) HIP_TRY(hipEventCreateWithFlags(&c->ev_index[slot], hipEventDisableTiming));
-        if (c->index_used[slot]) HIP_TRY(hipEventSynchronize(c->ev_index[slot])); // the launch that had this region 16 calls ago
-        void *scratch = c->d_index_scratch + brx_ix_region_bytes(c->index_cap_n, c->index_cap_tiles) * slot;
+        int rc = ring_reserve(c->index_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
+                              brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                              "index scratch allocation failed");
+        void *scratch = nullptr;
+        if (rc == BRX_SUCCESS) rc = ring_take(c->index_ring, &scratch);
+        if (rc != BRX_SUCCESS) return rc;
         // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
         brx_launch_index(out, out_off, len, n, span, delim, scratch, max_tiles, count, pos_off, pos, total, c->max_grid / 4u, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_index[slot], st));
-        c->index_used[slot] = true;
+        if ((rc = ring_record(c->index_ring, st)) != BRX_SUCCESS) return rc;
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;

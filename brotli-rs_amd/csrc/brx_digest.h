@@ -9,10 +9,7 @@
 #pragma once
 #include <stdint.h>
 
-#define BRX_DG_ROW 1024u            // bytes a wavefront reads per step: 64 lanes x 16 B, 1 KiB aligned
-#define BRX_DG_TILE_ROWS 64u
-#define BRX_DG_TILE (BRX_DG_ROW * BRX_DG_TILE_ROWS) // one work item: 64 KiB of a stream's (1 KiB aligned) address range
-#define BRX_DG_WG 512u              // threads per workgroup of the tile kernel: 8 waves share one copy of the LDS tables
+#include "brx_tiles.h"
 
 // Table block of one kind, in 32-bit words:
 #define BRX_DG_SLICE 0u             // 16 x 256: SLICE[j][b] = raw CRC of byte b followed by 15 - j zero bytes (byte j of a 16-byte chunk)
@@ -21,6 +18,13 @@
 #define BRX_DG_SMALLPOW 5120u       // 2048:     x^(8 d), d < 2048: a lane's distance to the end of its tile
 #define BRX_DG_POW 7168u            // 32:       x^(8 * 2^k): the squares for square-and-multiply over the bits of a byte count
 #define BRX_DG_WORDS 7200u
+
+// Scratch region of one launch: the header of the tile pass (brx_tiles.h), then one accumulator word per stream.
+static inline size_t brx_dg_region_bytes(size_t cap_n) { return brx_tp_region_bytes(cap_n, cap_n * 4u); }
+
+// brx_digest.hip: plan, tiles and fold on `hip_stream`
+void brx_launch_digest(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, const uint32_t *tab, uint32_t poly,
+                       void *scratch, uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, unsigned workgroups, void *hip_stream);
 
 // ---- host side: the table block from the polynomial ----
 // a * b mod P (bit 31 = x^0)

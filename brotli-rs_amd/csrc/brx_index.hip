@@ -1,13 +1,11 @@
 // brx_index.hip -- brx_index_batch: where the records of every decoded stream of a batch end, on the device (layout: brx_index.h).
 //
-// Count mode is two launches on the caller's stream, fill mode four:
-//   plan   one workgroup: tiles per stream (a tile = 64 KiB of the stream's 1 KiB aligned address range), their exclusive prefix sum,
-//          `count` and the two ticket counters cleared.  The host never learns a length.
-//   count  persistent grid, 4 workgroups of 8 waves per CU.  A work item is one (stream, tile) pair: a wave's first item is its index
-//          in the grid, the following ones come from a ticket counter.  The wave walks its tile in aligned 1 KiB rows, 16 B per lane,
-//          compares the four dwords of its chunk with the delimiter by packed arithmetic, and adds the population count to a per-lane
-//          sum.  At the tile's end the lanes add up; the tile's count goes to the tile's scratch word (fill mode) and, by one atomic
-//          add, to count[i] (addition commutes: tiles finish in any order and nobody waits for anybody).
+// Count mode is two launches on the caller's stream, fill mode four, in the shape of the tile pass (brx_tiles.h: tiling, plan, ticket
+// counters, item search):
+//   plan   brx_tiles.hip, with `count` cleared.
+//   count  a pass over the bytes: the wave compares the four dwords of its chunk with the delimiter by packed arithmetic, and adds the
+//          population count to a per-lane sum.  At the tile's end the lanes add up; the tile's count goes to the tile's scratch word
+//          (fill mode) and, by one atomic add, to count[i] (addition commutes: tiles finish in any order and nobody waits for anybody).
 //   scan   one workgroup: the tile counts -> their exclusive prefix sum G over ALL tiles of the batch, in place.  Tile t of stream i
 //          starts at delimiter G[t] - G[first tile of i] of its stream.
 //   fill   the same grid over the same items.  Per row: every lane's matches as a 16-bit mask, a wave prefix sum of their population
@@ -18,48 +16,6 @@
 #include <stdint.h>
 
 #include "brx_index.h"
-
-// a value that is the same in every lane of the wave, said so to the compiler: what depends on it is loaded by the scalar unit
-__device__ __forceinline__ uint64_t ix_uniform(uint64_t v) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
-           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
-}
-
-// tiles of a stream of l bytes whose first byte is at address a
-__device__ __forceinline__ uint64_t ix_tiles(uint64_t a, uint64_t l) {
-    return l ? ((a & (BRX_IX_ROW - 1u)) + l + BRX_IX_TILE - 1u) / BRX_IX_TILE : 0u;
-}
-
-__global__ __launch_bounds__(1024) void brx_index_plan_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
-                                                              const uint64_t *__restrict__ len, uint32_t n, uint64_t *__restrict__ pre,
-                                                              uint64_t *__restrict__ count, unsigned long long *ticket_a,
-                                                              unsigned long long *ticket_c) {
-    __shared__ uint64_t part[1024];
-    const uint32_t t = threadIdx.x;
-    const uint64_t per = ((uint64_t)n + 1023u) / 1024u;
-    const uint64_t i0 = per * t < n ? per * t : n, i1 = i0 + per < n ? i0 + per : n;
-    uint64_t sum = 0;
-    for (uint64_t i = i0; i < i1; i++) sum += ix_tiles((uint64_t)(uintptr_t)out + out_off[i], len[i]);
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t s = 1; s < 1024u; s <<= 1) { // inclusive scan of the 1024 partial sums
-        const uint64_t v = t >= s ? part[t - s] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - sum;
-    for (uint64_t i = i0; i < i1; i++) {
-        pre[i] = run;
-        if (count) count[i] = 0u;
-        run += ix_tiles((uint64_t)(uintptr_t)out + out_off[i], len[i]);
-    }
-    if (t == 1023u) {
-        pre[n] = part[1023];
-        *ticket_a = 0ull;
-        *ticket_c = 0ull;
-    }
-}
 
 // 0x80 in every byte of w that equals the delimiter (d4 = the delimiter in all four bytes).  x = w ^ d4 has a zero byte there; the sum
 // of a byte's low seven bits and 0x7F carries into bit 7 exactly when they are not all zero and never into the next byte, so the test
@@ -87,7 +43,7 @@ __device__ __forceinline__ uint4 ix_chunk(const uint8_t *out, uint64_t row, uint
                                           uint64_t arena1, uint32_t nd4) {
     const uint64_t c = row + 16u * lane;
     const uint8_t *pc = out + (int64_t)(c - arena0); // (from the kernel's argument: a global load, not a flat one)
-    if (row >= a && row + BRX_IX_ROW <= e) return *(const uint4 *)pc; // (uniform) a row inside the stream
+    if (row >= a && row + BRX_TP_ROW <= e) return *(const uint4 *)pc; // (uniform) a row inside the stream
     uint4 v = make_uint4(nd4, nd4, nd4, nd4);
     if (c < e && c + 16u > a) {
         const uint32_t lo = a > c ? (uint32_t)(a - c) : 0u, hi = e < c + 16u ? (uint32_t)(e - c) : 16u; // bytes [lo, hi) are the stream's
@@ -113,60 +69,23 @@ __device__ __forceinline__ uint4 ix_chunk(const uint8_t *out, uint64_t row, uint
     return v;
 }
 
-struct IxItem {
-    uint32_t si;  // the stream
-    uint64_t a;   // address of its first byte
-    uint64_t e;   // one past its last
-    uint64_t t0;  // address of the tile's first row
-    uint32_t rows;
-};
-
-// the stream of an item: the last i < n with pre[i] <= item (streams without tiles share their successor's value and lose)
-__device__ __forceinline__ IxItem ix_item(uint64_t item, const uint8_t *out, const uint64_t *__restrict__ out_off,
-                                          const uint64_t *__restrict__ len, uint32_t n, const uint64_t *__restrict__ pre) {
-    uint32_t lo_i = 0, hi_i = n;
-    while (hi_i - lo_i > 1u) {
-        const uint32_t mid = lo_i + (hi_i - lo_i) / 2u;
-        if (pre[mid] <= item) lo_i = mid; else hi_i = mid;
-    }
-    IxItem it;
-    it.si = lo_i;
-    it.a = (uint64_t)(uintptr_t)out + out_off[lo_i];
-    it.e = it.a + len[lo_i];
-    it.t0 = (it.a & ~(uint64_t)(BRX_IX_ROW - 1u)) + (item - pre[lo_i]) * BRX_IX_TILE;
-    const uint64_t t1 = it.t0 + BRX_IX_TILE < it.e ? it.t0 + BRX_IX_TILE : it.e;
-    it.rows = (uint32_t)((t1 - it.t0 + BRX_IX_ROW - 1u) / BRX_IX_ROW);
-    return it;
-}
-
-// the wave's next item: a load first (most waves end here, cheaply), the atomic only while there is something left
-__device__ __forceinline__ uint64_t ix_next(unsigned long long *ticket, uint64_t grid_waves, uint64_t total, uint32_t lane) {
-    unsigned long long next = 0;
-    if (lane == 0u) {
-        next = __hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (grid_waves + next < total) next = atomicAdd(ticket, 1ull);
-    }
-    next = (unsigned long long)__shfl((long long)next, 0);
-    return ix_uniform(grid_waves + next);
-}
-
-__global__ __launch_bounds__(BRX_IX_WG, 8) void brx_index_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
                                                                        const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
                                                                        uint32_t delim, const uint64_t *__restrict__ pre,
                                                                        uint64_t max_tiles, uint64_t *__restrict__ tile_cnt,
                                                                        uint64_t *count, unsigned long long *ticket) {
     const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles; // (more tiles than `span` allows: a caller's error, nothing is written for them)
-    const uint32_t waves_per_wg = BRX_IX_WG / 64u;
+    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
     const uint32_t d4 = delim * 0x01010101u, nd4 = ~d4;
     const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = ix_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
+    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
     while (item < total) {
-        const IxItem it = ix_item(item, out, out_off, len, n, pre);
+        const TpItem it = tp_item(item, out, out_off, len, n, pre);
         uint32_t acc = 0;
         for (uint32_t r = 0; r < it.rows; r++) {
-            const uint4 v = ix_chunk(out, it.t0 + (uint64_t)r * BRX_IX_ROW, lane, it.a, it.e, arena0, arena1, nd4);
+            const uint4 v = ix_chunk(out, it.t0 + (uint64_t)r * BRX_TP_ROW, lane, it.a, it.e, arena0, arena1, nd4);
             acc += __popc(ix_eq(v.x, d4)) + __popc(ix_eq(v.y, d4)) + __popc(ix_eq(v.z, d4)) + __popc(ix_eq(v.w, d4));
         }
 #pragma unroll
@@ -175,7 +94,7 @@ __global__ __launch_bounds__(BRX_IX_WG, 8) void brx_index_count_kernel(const uin
             if (tile_cnt) tile_cnt[item] = acc;
             if (count && acc) atomicAdd((unsigned long long *)&count[it.si], (unsigned long long)acc);
         }
-        item = ix_next(ticket, grid_waves, total, lane);
+        item = tp_next(ticket, grid_waves, total, lane);
     }
 }
 
@@ -188,15 +107,7 @@ __global__ __launch_bounds__(1024) void brx_index_scan_kernel(uint32_t n, const 
     const uint64_t i0 = per * t < total ? per * t : total, i1 = i0 + per < total ? i0 + per : total;
     uint64_t sum = 0;
     for (uint64_t i = i0; i < i1; i++) sum += tile_cnt[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t s = 1; s < 1024u; s <<= 1) {
-        const uint64_t v = t >= s ? part[t - s] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - sum;
+    uint64_t run = tp_block_scan_1024(part, t, sum) - sum;
     for (uint64_t i = i0; i < i1; i++) {
         const uint64_t c = tile_cnt[i];
         tile_cnt[i] = run;
@@ -204,25 +115,25 @@ __global__ __launch_bounds__(1024) void brx_index_scan_kernel(uint32_t n, const 
     }
 }
 
-__global__ __launch_bounds__(BRX_IX_WG, 8) void brx_index_fill_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_fill_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
                                                                       const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
                                                                       uint32_t delim, const uint64_t *__restrict__ pre,
                                                                       uint64_t max_tiles, const uint64_t *__restrict__ tile_base,
                                                                       const uint64_t *__restrict__ pos_off, uint64_t *__restrict__ pos,
                                                                       uint64_t pos_total, unsigned long long *ticket) {
     const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
-    const uint32_t waves_per_wg = BRX_IX_WG / 64u;
+    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
     const uint32_t d4 = delim * 0x01010101u, nd4 = ~d4;
     const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = ix_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
+    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
     while (item < total) {
-        const IxItem it = ix_item(item, out, out_off, len, n, pre);
+        const TpItem it = tp_item(item, out, out_off, len, n, pre);
         // index in pos of the tile's first delimiter: the stream's first entry + the delimiters of the stream's tiles in front of this one
-        uint64_t base = ix_uniform(pos_off[it.si] + (tile_base[item] - tile_base[pre[it.si]]));
+        uint64_t base = tp_uniform(pos_off[it.si] + (tile_base[item] - tile_base[pre[it.si]]));
         for (uint32_t r = 0; r < it.rows; r++) {
-            const uint64_t row = it.t0 + (uint64_t)r * BRX_IX_ROW;
+            const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
             const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, nd4);
             uint32_t m = ix_nib(ix_eq(v.x, d4)) | (ix_nib(ix_eq(v.y, d4)) << 4) | (ix_nib(ix_eq(v.z, d4)) << 8) |
                          (ix_nib(ix_eq(v.w, d4)) << 12); // bit k: byte k of the chunk is a delimiter of the stream
@@ -244,24 +155,20 @@ __global__ __launch_bounds__(BRX_IX_WG, 8) void brx_index_fill_kernel(const uint
             }
             base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         }
-        item = ix_next(ticket, grid_waves, total, lane);
+        item = tp_next(ticket, grid_waves, total, lane);
     }
 }
 
 void brx_launch_index(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint8_t delim,
                       void *scratch, uint64_t max_tiles, uint64_t *count, const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                       unsigned workgroups, void *hip_stream) {
-    unsigned long long *ticket_a = (unsigned long long *)((uint8_t *)scratch + BRX_IX_TICKET_A);
-    unsigned long long *ticket_c = (unsigned long long *)((uint8_t *)scratch + BRX_IX_TICKET_C);
-    uint64_t *pre = (uint64_t *)((uint8_t *)scratch + BRX_IX_PRE);
-    uint64_t *tiles = pre + (size_t)n + 1u;
+    uint64_t *pre = brx_tp_pre(scratch), *tiles = (uint64_t *)brx_tp_own(scratch, n);
     hipStream_t st = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(brx_index_plan_kernel, dim3(1), dim3(1024), 0, st, (const uint8_t *)out, out_off, len, n, pre, count, ticket_a,
-                       ticket_c);
-    hipLaunchKernelGGL(brx_index_count_kernel, dim3(workgroups), dim3(BRX_IX_WG), 0, st, (const uint8_t *)out, out_off, len, n, span,
-                       (uint32_t)delim, pre, max_tiles, pos ? tiles : nullptr, count, ticket_a);
+    brx_launch_tile_plan(out, out_off, len, n, scratch, (uint32_t *)count, count ? 2u : 0u, st);
+    hipLaunchKernelGGL(brx_index_count_kernel, dim3(workgroups), dim3(BRX_TP_WG), 0, st, (const uint8_t *)out, out_off, len, n, span,
+                       (uint32_t)delim, pre, max_tiles, pos ? tiles : nullptr, count, brx_tp_ticket_a(scratch));
     if (!pos) return;
     hipLaunchKernelGGL(brx_index_scan_kernel, dim3(1), dim3(1024), 0, st, n, pre, max_tiles, tiles);
-    hipLaunchKernelGGL(brx_index_fill_kernel, dim3(workgroups), dim3(BRX_IX_WG), 0, st, (const uint8_t *)out, out_off, len, n, span,
-                       (uint32_t)delim, pre, max_tiles, tiles, pos_off, pos, total, ticket_c);
+    hipLaunchKernelGGL(brx_index_fill_kernel, dim3(workgroups), dim3(BRX_TP_WG), 0, st, (const uint8_t *)out, out_off, len, n, span,
+                       (uint32_t)delim, pre, max_tiles, tiles, pos_off, pos, total, brx_tp_ticket_b(scratch));
 }

@@ -27,7 +27,7 @@ def test_digest_batch_is_declared_and_exported():
     assert brx.load_library().brx_digest_batch is not None
     assert "brx_digest_batch" in brx.EXPORTED_SYMBOLS
     blob = open(path, "rb").read()
-    for kernel in (b"brx_digest_plan_kernel", b"brx_digest_tiles_kernel", b"brx_digest_fold_kernel"):
+    for kernel in (b"brx_tile_plan_kernel", b"brx_digest_tiles_kernel", b"brx_digest_fold_kernel"):
         assert kernel in blob  # the pass is native code in the library, next to the decode kernels
 
 

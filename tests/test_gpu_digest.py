@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest.json")))
-TILE = 65536  # one work item of the pass (brx_digest.h); the tests below only choose lengths around it
+TILE = 65536  # one work item of the pass (brx_tiles.h); the tests below only choose lengths around it
 
 _C_TABLE = np.zeros(256, dtype=np.uint32)
 for _i in range(256):

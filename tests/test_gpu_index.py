@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest.json")))
-TILE = 65536  # one work item of the pass (brx_index.h); the tests below only choose lengths and addresses around it
+TILE = 65536  # one work item of the pass (brx_tiles.h); the tests below only choose lengths and addresses around it
 SENTINEL = -0x0123456789ABCDEF
 DELIMS = (0x0A, 0x00, 0x80, 0xFF)
 

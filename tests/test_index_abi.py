@@ -28,7 +28,7 @@ def test_index_batch_is_declared_and_exported():
     assert brx.load_library().brx_index_batch is not None
     assert "brx_index_batch" in brx.EXPORTED_SYMBOLS
     blob = open(path, "rb").read()
-    for kernel in (b"brx_index_plan_kernel", b"brx_index_count_kernel", b"brx_index_scan_kernel", b"brx_index_fill_kernel"):
+    for kernel in (b"brx_tile_plan_kernel", b"brx_index_count_kernel", b"brx_index_scan_kernel", b"brx_index_fill_kernel"):
         assert kernel in blob  # the pass is native code in the library, next to the decode kernels
 
 
