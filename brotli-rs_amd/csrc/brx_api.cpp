@@ -141,6 +141,8 @@ struct brx_ctx {
     uint32_t *d_order = nullptr;
     size_t order_cap = 0;
     const uint32_t *last_counter = nullptr; // counter line of the most recent launch (brx_last_timing(ctx, 2))
+    uint32_t last_lean_head = 0;            // ... and the streams above the lean instance's limit that it never saw: the head of a
+                                            // host-made queue order (brx_last_timing(ctx, 5) counts them with the listed ones)
     uint32_t tiny_bytes = BRX_TINY_STREAM_BYTES; // bring-up / A-B: BRX_TINY_BYTES
     bool no_defer = false; // bring-up / A-B (BRX_NO_DEFER=1): spilled meta-blocks stay in the regular kernel's C++ loop
     uint32_t small_bytes = BRX_SMALL_STREAM_BYTES; // streams up to this size go to the lean instance first (0: there is none)
@@ -885,6 +887,7 @@ static int launch(brx_ctx *c, hipStream_t st, const LaunchReq &r) {
         c->inflight_waves[ring_slot] = slab_waves;
     }
     if (!r.desc) c->last_counter = (a.defer != nullptr || lean) ? a.work_counter : nullptr;
+    if (!r.desc) c->last_lean_head = lean_tail ? r.n_large : 0u; // (no lean launch: brx_last_timing(ctx, 5) reads 0)
     c->any_launch = true;
 #ifdef BRX_BRINGUP
     if (a.dump) { // bring-up: parked decoder states for tools/asm_emu.py
@@ -1133,7 +1136,7 @@ extern "C" double brx_last_timing(brx_ctx *c, int which) {
         case 2: return (double)w[BRX_WC_LIST] + w[BRX_WC_LIST + 1] + w[BRX_WC_LIST + 2] + late;
         case 3: return (double)w[BRX_WC_LIST + 1] + w[BRX_WC_LIST + 2];
         case 4: return (double)w[BRX_WC_LIST + 2];
-        case 5: return (double)w[BRX_WC_LEAN_LISTED];
+        case 5: return (double)w[BRX_WC_LEAN_LISTED] + c->last_lean_head; // (listed on the device + left out of its queue by the host)
         case 6: return (double)late;
         default: return (double)w[BRX_WC_TWICE];
         }

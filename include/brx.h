@@ -197,7 +197,8 @@ const char *brx_last_error(void);
  * kernel that holds them -- 9 472 / 17 152 / 37 632 B of table memory, 12 / 8 / 4 instead of 16 streams per CU:
  *   2, 3, 4  streams decoded at level >= 1, >= 2, 3 (2 = every stream that left the regular kernel)
  *   5        streams the lean instance (short streams, 32 per CU, launched in front of the regular kernel) left to the regular
- *            kernel -- the ones above its size limit plus the short ones it gave up on (any error, block switches, large tables)
+ *            kernel -- the ones above its size limit plus the short ones it gave up on (any error, block switches, large tables);
+ *            0 when the launch had no lean instance in front (BRX_OPTION_SMALL_BYTES 0, no stream within the limit, a reader round)
  *   6        streams that were handed up at a LATER meta-block, with their decoder state (resumed there, not restarted)
  *   7        output bytes decoded twice because of hand-overs (0 = every such stream was resumed where it stood)
  *   8        (since the context was made) slices of bounded / pulled streams that paused in front of an item -- a header, an

@@ -407,7 +407,14 @@ typedef struct {
     unsigned flags;
     size_t needed;         /* for BRO_OUTPUT_TOO_SMALL */
     bro_stats st;
+    uint32_t *codes;       /* bro_decode_codes: the record list, its capacity, records so far, compressed meta-blocks so far */
+    size_t codes_cap, n_codes, n_cmb;
 } Dec;
+
+static void note_code(Dec *d, unsigned category, unsigned nsym) {
+    if (d->n_codes < d->codes_cap) d->codes[d->n_codes] = (uint32_t)(d->n_cmb << 12) | (category << 10) | nsym;
+    d->n_codes++;
+}
 
 static const char *const STATUS_STR[28] = {
     "OK",
@@ -729,6 +736,7 @@ static int parse_context_map(Dec *d, unsigned ntrees, uint8_t *cmap, size_t len)
         uint32_t v;
         if (br_bits(&d->br, 4, &v)) return BRO_UNEXPECTED_EOF;
         rlemax = v + 1;
+        d->st.cmap_rle++;
     }
     PCode pc;
     int rc = parse_prefix_code(d, rlemax + ntrees, &pc);
@@ -757,7 +765,10 @@ static int parse_context_map(Dec *d, unsigned ntrees, uint8_t *cmap, size_t len)
     if (rc) return rc;
     b = br_bit(&d->br);
     if (b < 0) return BRO_UNEXPECTED_EOF;
-    if (b) bro_inverse_mtf(cmap, len);
+    if (b) {
+        bro_inverse_mtf(cmap, len);
+        d->st.cmap_imtf++;
+    }
     return 0;
 }
 
@@ -833,6 +844,28 @@ static int compressed_meta_block(Dec *d, size_t mlen) {
     for (unsigned i = 0; i < ntrees_d; i++) /* parse_prefix_codes_distances :1052 */
         if ((rc = parse_prefix_code(d, dist_alphabet, &dst[i]))) goto out;
 
+    { /* census of the header */
+        unsigned nbl = L.nbl > I.nbl ? L.nbl : I.nbl;
+        if (D.nbl > nbl) nbl = D.nbl;
+        if (nbl > d->st.max_block_types) d->st.max_block_types = nbl;
+        d->st.npostfix_mask |= 1ull << npostfix;
+        d->st.ndirect_mask |= ndirect ? 2u : 1u;
+        d->st.ntrees_l_mask |= 1ull << (16 * cmode[0] + (ntrees_l < 15 ? ntrees_l : 15));
+        d->st.ntrees_d_mask |= 1ull << (ntrees_d < 63 ? ntrees_d : 63);
+        for (unsigned i = 0; i < ntrees_l; i++) {
+            note_code(d, 0, lit[i].nsym);
+            if (lit[i].nsym == 1) d->st.single_codes |= 1;
+        }
+        for (unsigned i = 0; i < n_iac; i++) {
+            note_code(d, 1, iac[i].nsym);
+            if (iac[i].nsym == 1) d->st.single_codes |= 2;
+        }
+        for (unsigned i = 0; i < ntrees_d; i++) {
+            note_code(d, 2, dst[i].nsym);
+            if (dst[i].nsym == 1) d->st.single_codes |= 4;
+        }
+        d->n_cmb++;
+    }
     const uint8_t *LUT0 = BRO_CONTEXT_LUT, *LUT1 = BRO_CONTEXT_LUT + 256, *LUT2 = BRO_CONTEXT_LUT + 512;
     size_t mb_count = 0; /* MetaBlock.count_output */
 
@@ -852,6 +885,7 @@ static int compressed_meta_block(Dec *d, size_t mlen) {
         bro_insert_copy_entry(sym, &ib, &ie, &cb, &ce);
         if (br_bits(&d->br, ie, &extra)) { rc = BRO_UNEXPECTED_EOF; goto out; }
         size_t insert_len = ib + extra;
+        if (ie > d->st.max_insert_extra) d->st.max_insert_extra = ie;
         if (br_bits(&d->br, ce, &extra)) { rc = BRO_UNEXPECTED_EOF; goto out; }
         size_t copy_len = cb + extra;
         if (mlen < mb_count + insert_len) { rc = BRO_EXCEEDED_EXPECTED_BYTES; goto out; } /* :2036 (Q4) */
@@ -901,6 +935,11 @@ static int compressed_meta_block(Dec *d, size_t mlen) {
             lk = pcode_lookup(&dst[idx], &d->br, &dcode);
             if (lk == LK_NONE) { rc = BRO_PARSE_ERROR_DISTANCE_CODE; goto out; }
             if (lk == LK_EOF) { rc = BRO_UNEXPECTED_EOF; goto out; }
+            d->st.dist_code_mask |= 1ull << (dcode <= 15 ? dcode : dcode <= 15 + ndirect ? 16 : 17);
+            if (ntrees_d > 1) {
+                d->st.dist_ctx_mask |= 1ull << cid;
+                if (idx < 4) d->st.dist_ctx_trees |= 1ull << (4 * cid + idx);
+            }
         }
         /* decode_distance :1412-1481 */
         uint64_t distance;
@@ -958,6 +997,13 @@ static int compressed_meta_block(Dec *d, size_t mlen) {
             mb_count += copy_len;
             d->st.copies++;
             d->st.copy_bytes += copy_len;
+            if (copy_len > d->st.max_copy_len) d->st.max_copy_len = copy_len;
+            if (copy_len < 64) d->st.copy_len_lo |= 1ull << copy_len;
+            if (distance < 16) d->st.short_dist_mask |= 1ull << distance;
+            if (distance == copy_len) d->st.dist_eq_len++;
+            if (distance > copy_len) d->st.dist_gt_len++;
+            if (distance == max_allowed) d->st.dist_at_max++;
+            if (implicit_zero) d->st.implicit_dist0++;
             if (distance > d->st.max_distance) d->st.max_distance = distance;
         } else {
             if (copy_len < 4 || copy_len > 24) { rc = BRO_INVALID_LENGTH_IN_STATIC_DICTIONARY; goto out; }
@@ -978,6 +1024,10 @@ static int compressed_meta_block(Dec *d, size_t mlen) {
             mb_count += (size_t)wl;
             d->st.dict_refs++;
             d->st.dict_bytes += (uint64_t)wl;
+            d->st.dict_len_mask |= 1ull << copy_len;
+            if (transform_id < 64) d->st.xform_lo |= 1ull << transform_id;
+            else d->st.xform_hi |= 1ull << (transform_id - 64);
+            if (implicit_zero) d->st.implicit_dist0++;
         }
         sync_ctx(d); /* every copied byte goes through literal_buf too (:2117) */
         if (mb_count == mlen) break; /* :2128 */
@@ -1003,6 +1053,11 @@ out:
 /* ------------------------------------------------------------------------- */
 int bro_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *out_len, unsigned flags,
                bro_stats *stats) {
+    return bro_decode_codes(in, in_len, out, out_cap, out_len, flags, stats, NULL, 0, NULL);
+}
+
+int bro_decode_codes(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *out_len, unsigned flags,
+                     bro_stats *stats, uint32_t *codes, size_t codes_cap, size_t *n_codes) {
     bro_init();
     g_trace = getenv("BRO_TRACE") ? atoi(getenv("BRO_TRACE")) : 0;
     if (getenv("BRO_TRACE") && !g_trace) g_trace = 1; /* read once per stream: keeps the command loop free of libc calls */
@@ -1013,6 +1068,8 @@ int bro_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, s
     d.out = out;
     d.cap = out_cap;
     d.flags = flags;
+    d.codes = codes;
+    d.codes_cap = codes ? codes_cap : 0;
     d.dist[0] = 4; /* RingBuffer::from_vec(vec![4, 11, 15, 16]): nth(0) == 4 */
     d.dist[1] = 11;
     d.dist[2] = 15;
@@ -1023,6 +1080,7 @@ int bro_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, s
 
     if ((rc = parse_wbits(&d, &wbits))) goto fin;
     d.window = ((size_t)1 << wbits) - 16;
+    d.st.wbits = wbits;
 
     for (;;) { /* HeaderMetaBlockBegin :1572 */
         int is_last = br_bit(&d.br); /* parse_is_last :420 */
@@ -1030,11 +1088,15 @@ int bro_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, s
         if (is_last) {
             int empty = br_bit(&d.br); /* parse_is_last_empty :427 */
             if (empty < 0) { rc = BRO_UNEXPECTED_EOF; goto fin; }
-            if (empty) break;
+            if (empty) {
+                d.st.empty_last = 1;
+                break;
+            }
         }
         if (br_bits(&d.br, 2, &v)) { rc = BRO_UNEXPECTED_EOF; goto fin; } /* parse_m_nibbles :434 */
         unsigned mnibbles = (v == 3) ? 0 : v + 4;
         if (mnibbles == 0) { /* metadata block, accepted even when ISLAST (Q9); states :1617-1683 */
+            d.st.metadata_blocks++;
             int reserved = br_bit(&d.br);
             if (reserved < 0) { rc = BRO_UNEXPECTED_EOF; goto fin; }
             if (reserved) { rc = BRO_NON_ZERO_RESERVED_BIT; goto fin; }
@@ -1068,7 +1130,9 @@ int bro_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, s
                 if (uncompressed < 0) { rc = BRO_UNEXPECTED_EOF; goto fin; }
             }
             d.st.meta_blocks++;
+            d.st.mnibbles_mask |= 1ull << mnibbles;
             if (uncompressed) { /* :1701-1734 */
+                d.st.raw_blocks++;
                 if (br_byte_tail(&d.br) != 0) { rc = BRO_NON_ZERO_FILL_BIT; goto fin; }
                 if (d.br.pos + 8ull * mlen > d.br.nbits) { rc = BRO_UNEXPECTED_EOF; goto fin; }
                 if ((rc = out_room(&d, mlen))) goto fin;
@@ -1095,5 +1159,6 @@ fin:
     *out_len = (rc == BRO_OUTPUT_TOO_SMALL && d.needed) ? d.needed : d.pos;
     d.st.bits_consumed = d.br.pos;
     if (stats) *stats = d.st;
+    if (n_codes) *n_codes = d.n_codes;
     return rc;
 }

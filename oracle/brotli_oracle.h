@@ -77,6 +77,35 @@ typedef struct {
     uint64_t block_switches;   /* block-switch commands, all three categories */
     uint64_t bits_consumed;    /* input bits consumed */
     uint64_t max_distance;     /* largest window distance used */
+    /* What the header of the stream and of its meta-blocks says (masks: bit k = value k was seen). */
+    uint64_t wbits;            /* WBITS */
+    uint64_t metadata_blocks;  /* metadata meta-blocks (MNIBBLES code 3) */
+    uint64_t mnibbles_mask;    /* MNIBBLES of the other meta-blocks (bits 4..6) */
+    uint64_t max_block_types;  /* largest NBLTYPES of any category */
+    uint64_t npostfix_mask;    /* NPOSTFIX of compressed meta-blocks (bits 0..3) */
+    uint64_t ndirect_mask;     /* bit 0: a compressed meta-block with NDIRECT = 0, bit 1: one with NDIRECT > 0 */
+    uint64_t ntrees_l_mask;    /* NTREESL by context mode of block type 0: bit (16 * mode + min(NTREESL, 15)) */
+    uint64_t ntrees_d_mask;    /* NTREESD: bit min(NTREESD, 63) */
+    uint64_t cmap_rle;         /* context maps with RLEMAX > 0 */
+    uint64_t cmap_imtf;        /* context maps with the inverse move-to-front bit set */
+    uint64_t single_codes;     /* one-symbol prefix codes: bit 0 literal, bit 1 insert&copy, bit 2 distance */
+    /* What the commands do. */
+    uint64_t max_insert_extra; /* most extra bits of an insert length */
+    uint64_t max_copy_len;     /* longest copy length of a window copy */
+    uint64_t copy_len_lo;      /* window copies of length 2..63: bit = length */
+    uint64_t implicit_dist0;   /* window copies / dictionary words of commands with the implicit distance code 0 (symbol < 128) */
+    uint64_t dist_code_mask;   /* distance symbols read: bits 0..15 the ring codes, bit 16 a direct code, bit 17 one with extra bits */
+    uint64_t dist_ctx_mask;    /* distance contexts (bits 0..3) of the symbols read while NTREESD > 1 */
+    uint64_t dist_ctx_trees;   /* ... bit (4 * context + tree) for trees 0..3 */
+    uint64_t short_dist_mask;  /* window copies of distance 1..15: bit = distance */
+    uint64_t dist_eq_len;      /* window copies with distance == length */
+    uint64_t dist_gt_len;      /* ... with distance > length */
+    uint64_t dist_at_max;      /* ... with distance == min(position, window size) */
+    uint64_t dict_len_mask;    /* copy lengths of dictionary words (bits 4..24) */
+    uint64_t xform_lo;         /* transform ids 0..63 of dictionary words */
+    uint64_t xform_hi;         /* transform ids 64..120 (bit = id - 64) */
+    uint64_t raw_blocks;       /* uncompressed meta-blocks */
+    uint64_t empty_last;       /* 1: the stream ends with ISLAST + ISLASTEMPTY */
 } bro_stats;
 
 /* Decode one whole stream.  `out` doubles as the sliding window.  Returns a status code.
@@ -84,6 +113,12 @@ typedef struct {
  * produced before the error (NOT a stable observable of the reference). */
 int bro_decode(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *out_len,
                unsigned flags, bro_stats *stats /* may be NULL */);
+
+/* The same, and one record per prefix code of the three command categories, in stream order, into codes[0 .. codes_cap):
+ * meta-block index (compressed ones, from 0) << 12 | category << 10 (0 literal, 1 insert&copy, 2 distance) | symbols with a
+ * codeword (1 .. 704).  *n_codes = records there are (may exceed codes_cap: the rest is not stored). */
+int bro_decode_codes(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *out_len, unsigned flags,
+                     bro_stats *stats, uint32_t *codes, size_t codes_cap, size_t *n_codes);
 
 /* The exact description strings of src/lib.rs:331-354 (typos included); 25/26 get this build's text. */
 const char *bro_status_str(int status);

@@ -255,6 +255,15 @@ def iac_symbol(insert_len, copy_len):
     return sym, (insert_len - INS_BASE[ic], INS_EXTRA[ic]), (copy_len - CPY_BASE[cc], CPY_EXTRA[cc])
 
 
+def iac_symbol_implicit(insert_len, copy_len):
+    """The same for a symbol below 128: insert code 0..7, copy code 0..15, and the distance is the last one with no symbol read."""
+    ic = max(c for c in range(24) if INS_BASE[c] <= insert_len)
+    cc = max(c for c in range(24) if CPY_BASE[c] <= copy_len)
+    assert ic < 8 and cc < 16, (insert_len, copy_len)
+    sym = 64 * (cc >> 3) + 8 * ic + (cc & 7)
+    return sym, (insert_len - INS_BASE[ic], INS_EXTRA[ic]), (copy_len - CPY_BASE[cc], CPY_EXTRA[cc])
+
+
 def distance_code(distance, npostfix=0, ndirect=0):
     """(code, extra value, extra bits) of an explicit distance (no ring codes), RFC 7932 section 4."""
     if distance <= ndirect:
@@ -273,10 +282,15 @@ def distance_code(distance, npostfix=0, ndirect=0):
 class MetaBlock:
     """One compressed meta-block with one block type per category, one literal tree (all 256 bytes, 8 bits each),
     a near-uniform insert&copy code over the symbols the commands use and a uniform distance code over the 64 symbols
-    of NPOSTFIX = NDIRECT = 0.  Commands: (literal bytes, copy_len, distance) -- distance None = no copy (last command)."""
+    of NPOSTFIX = NDIRECT = 0.  Commands: (literal bytes, copy_len, distance) -- distance None = no copy (last command),
+    "implicit" = an insert&copy symbol below 128 (the last distance, no distance symbol), ("code", k) = distance symbol k as it is
+    (the ring codes 0..15: no extra bits).  dist_used: the distance code covers only the symbols the commands use (and one more
+    when that is a single one) instead of the whole alphabet; mnibbles: MNIBBLES as given instead of the smallest that holds MLEN."""
 
-    def __init__(self, commands, mlen=None, npostfix=0, ndirect=0, lit_lengths=None, single_iac=False, single_dist=False, lit_cl_len=None):
+    def __init__(self, commands, mlen=None, npostfix=0, ndirect=0, lit_lengths=None, single_iac=False, single_dist=False, lit_cl_len=None,
+                 dist_used=False, mnibbles=None):
         self.commands, self.mlen, self.npostfix, self.ndirect = commands, mlen, npostfix, ndirect
+        self.dist_used, self.mnibbles = dist_used, mnibbles
         self.single_dist = single_dist  # a ONE-symbol distance code (every copy has the same distance code; zero bits per symbol; the
                                         # copies may still differ in the code's extra bits)
         self.lit_lengths = lit_lengths  # code lengths of the 256 literals (default: 8 bits each)
@@ -288,7 +302,7 @@ class MetaBlock:
         b.put(1 if is_last else 0, 1)
         if is_last:
             b.put(0, 1)  # ISLASTEMPTY
-        nib = 4 if mlen <= 1 << 16 else 5 if mlen <= 1 << 20 else 6
+        nib = self.mnibbles or (4 if mlen <= 1 << 16 else 5 if mlen <= 1 << 20 else 6)
         b.put(nib - 4, 2)
         b.put(mlen - 1, 4 * nib)
         if not is_last:
@@ -300,7 +314,14 @@ class MetaBlock:
         b.put(0, 1)   # NTREESL = 1
         b.put(0, 1)   # NTREESD = 1
         lit = complex_code(b, self.lit_lengths or [8] * 256, zero_run_17=self.lit_lengths is not None and self.lit_cl_len is None, cl_len=self.lit_cl_len)
-        syms = sorted({iac_symbol(len(l), c if c else 2)[0] for l, c, d in self.commands})
+        def iac_of(l, c, d):
+            return iac_symbol_implicit(len(l), c) if d == "implicit" else iac_symbol(len(l), c if c else 2)
+
+        def dcode_of(d):
+            return (d[1], 0, 0) if isinstance(d, tuple) else distance_code(d, self.npostfix, self.ndirect)
+
+        explicit = [d for l, c, d in self.commands if d is not None and d != "implicit"]
+        syms = sorted({iac_of(l, c, d)[0] for l, c, d in self.commands})
         if len(syms) == 1 and not self.single_iac:
             syms.append(syms[0] + 1 if syms[0] + 1 < 704 else syms[0] - 1)  # (a 1-symbol insert&copy code never enters the asm loop)
         if len(syms) == 1:
@@ -310,33 +331,38 @@ class MetaBlock:
             iac = complex_code(b, uniform_lengths(704, syms), zero_run_17=True)
         dalpha = 16 + self.ndirect + (48 << self.npostfix)
         if self.single_dist:
-            codes = sorted({distance_code(d, self.npostfix, self.ndirect)[0] for l, c, d in self.commands if d is not None})
+            codes = sorted({dcode_of(d)[0] for d in explicit})
             assert len(codes) == 1
             simple_code(b, codes, max(1, (dalpha - 1).bit_length()))
             dist = {codes[0]: (0, 0)}
+        elif self.dist_used:
+            codes = sorted({dcode_of(d)[0] for d in explicit}) or [0]
+            if len(codes) == 1:
+                codes.append(codes[0] + 1 if codes[0] + 1 < dalpha else codes[0] - 1)
+            dist = complex_code(b, uniform_lengths(dalpha, codes), zero_run_17=True)
         else:
             dist = complex_code(b, uniform_lengths(dalpha), zero_run_17=False)
         for lits, cl, d in self.commands:
-            sym, ie, ce = iac_symbol(len(lits), cl if cl else 2)
+            sym, ie, ce = iac_of(lits, cl, d)
             put_sym(b, iac, sym)
             b.put(*ie)
             b.put(*ce)
             for x in lits:
                 put_sym(b, lit, x)
-            if d is not None:
-                code, ev, eb = distance_code(d, self.npostfix, self.ndirect)
+            if d is not None and d != "implicit":
+                code, ev, eb = dcode_of(d)
                 put_sym(b, dist, code)
                 b.put(ev, eb)
 
 
-def raw_block(b, data):
-    """Uncompressed meta-block (ISLAST = 0)."""
+def raw_block(b, data, fill=0):
+    """Uncompressed meta-block (ISLAST = 0).  fill: the bits up to the byte boundary (anything but 0: NonZeroFillBit)."""
     assert 0 < len(data) <= 1 << 16
     b.put(0, 1)
     b.put(0, 2)
     b.put(len(data) - 1, 16)
     b.put(1, 1)  # ISUNCOMPRESSED
-    b.put(0, (-b.n) % 8)
+    b.put(fill & ((1 << ((-b.n) % 8)) - 1), (-b.n) % 8)
     b.put_bytes(data)
 
 
@@ -690,14 +716,92 @@ def growing_tables_stream(seed, trees_per_mb, mode=0, n_cmds=40, wbits=18, first
     return b.bytes(), bytes(out)
 
 
-def many_trees_stream(seed, ntl, ntd, nbl_l, nbl_d, n_cmds=400, wbits=18):
+def mtf_forward(values):
+    """Move-to-front transform of a context map: what an encoder sends when it sets the inverse move-to-front bit."""
+    lst, out = list(range(256)), []
+    for v in values:
+        i = lst.index(v)
+        out.append(i)
+        lst.insert(0, lst.pop(i))
+    return out
+
+
+def context_map(b, rng, ntrees, size, rlemax=0, imtf=False, cmap=None):
+    """NTREES and, from two trees on, a context map of `size` random entries (or `cmap`).  rlemax > 0: every stretch of 16 entries
+    holds a run of nine equal ones -- zeros, or with imtf any tree, which the move-to-front transform turns into zeros -- and the
+    zeros are sent as run-length codes 1 .. rlemax wherever one fits; the prefix code covers the symbols in use.  imtf: the map is
+    sent move-to-front transformed, with the inverse move-to-front bit set.  Returns the map."""
+    _nbltypes(b, ntrees)
+    if ntrees < 2:
+        return [0] * size
+    given = cmap is not None
+    cmap = list(cmap) if given else [rng.randrange(ntrees) for _ in range(size)]
+    assert len(cmap) == size and max(cmap) < ntrees
+    if not rlemax and not imtf:
+        b.put(0, 1)  # RLEMAX = 0
+        if ntrees <= 4:
+            simple_code(b, list(range(ntrees)), max(1, (ntrees - 1).bit_length()))
+            for c in cmap:
+                b.put(*code_bits(list(range(ntrees)), c))
+        else:
+            codes = complex_code(b, uniform_lengths(ntrees))
+            for c in cmap:
+                put_sym(b, codes, c)
+        b.put(0, 1)  # no inverse move-to-front
+        return cmap
+    if rlemax and not given:
+        for a in range(0, size, 16):
+            lo, hi = min(a + 3, size), min(a + 12, size)
+            cmap[lo:hi] = [cmap[lo - 1] if imtf and lo else 0] * (hi - lo)
+    seq = mtf_forward(cmap) if imtf else cmap
+    toks, i = [], 0  # (symbol, extra value, extra bits)
+    while i < size:
+        if seq[i]:
+            toks.append((seq[i] + rlemax, 0, 0))
+            i += 1
+            continue
+        j = i
+        while j < size and seq[j] == 0:
+            j += 1
+        r = j - i
+        while r:
+            k = min(rlemax, r.bit_length() - 1)
+            if k < 1:
+                toks.append((0, 0, 0))
+                r -= 1
+            else:
+                n = min(r, (2 << k) - 1)
+                toks.append((k, n - (1 << k), k))
+                r -= n
+        i = j
+    if rlemax:
+        b.put(1, 1); b.put(rlemax - 1, 4)
+    else:
+        b.put(0, 1)
+    alphabet = rlemax + ntrees
+    used = sorted({t[0] for t in toks})
+    if len(used) == 1:
+        simple_code(b, used, max(1, (alphabet - 1).bit_length()))
+        codes = {used[0]: (0, 0)}
+    else:
+        codes = complex_code(b, uniform_lengths(alphabet, used), zero_run_17=True)
+    for sym, ev, eb in toks:
+        put_sym(b, codes, sym)
+        b.put(ev, eb)
+    b.put(1 if imtf else 0, 1)
+    return cmap
+
+
+def many_trees_stream(seed, ntl, ntd, nbl_l, nbl_d, n_cmds=400, wbits=18, rlemax=0, imtf=False, mode=None, dmap=None, info=None):
     """One compressed meta-block with up to 256 literal and 256 distance trees behind context maps, nbl_l literal and nbl_d distance
     block types that SWITCH (block type symbols 0 = the one before, 1 = the next one; counts 1 .. 4 or 17 .. 24), what one piece of
     more than a megabyte looks like out of libbrotlienc (profiles/r05_big_trees.txt) at a size a test decodes in no time.  Every
     literal tree has two symbols (one bit per literal under ANY tree: the bytes that come out tell the trees apart), every distance
     tree two symbols -- one of the four last-distance codes and one explicit code of 1 or 2 extra bits; commands: 6 / 7 literals,
     then a copy of 2 .. 5 (all four distance contexts).  The caller takes the expected output from the oracle (the stream is
-    valid by construction: a model of the distance ring keeps every distance inside the output)."""
+    valid by construction: a model of the distance ring keeps every distance inside the output).  rlemax / imtf: the context maps
+    are sent that way (context_map);  mode: the literal context mode (default: drawn);  dmap: the distance context map;  info: a
+    dict that receives what was emitted -- mode, cmap_l, cmap_d, and dist_ctx_trees, the (distance context, tree) pairs used."""
     rng = random.Random(seed)
     b = Bits()
     stream_header(b, wbits)
@@ -740,29 +844,13 @@ def many_trees_stream(seed, ntl, ntd, nbl_l, nbl_d, n_cmds=400, wbits=18):
     D = category(nbl_d)
     b.put(0, 2)  # NPOSTFIX
     b.put(0, 4)  # NDIRECT
-    mode = rng.randrange(4)
+    drawn = rng.randrange(4)
+    mode = drawn if mode is None else mode
     for _ in range(nbl_l):
         b.put(mode, 2)  # (one context mode: the meta-block stays in the assembly loop across literal block switches)
-
-    def context_map(ntrees, size):
-        _nbltypes(b, ntrees)
-        if ntrees < 2:
-            return [0] * size
-        cmap = [rng.randrange(ntrees) for _ in range(size)]
-        b.put(0, 1)  # RLEMAX = 0
-        if ntrees <= 4:
-            simple_code(b, list(range(ntrees)), max(1, (ntrees - 1).bit_length()))
-            for c in cmap:
-                b.put(*code_bits(list(range(ntrees)), c))
-        else:
-            codes = complex_code(b, uniform_lengths(ntrees))
-            for c in cmap:
-                put_sym(b, codes, c)
-        b.put(0, 1)  # no inverse move-to-front
-        return cmap
-
-    context_map(ntl, 64 * nbl_l)
-    cmap_d = context_map(ntd, 4 * nbl_d)
+    cmap_l = context_map(b, rng, ntl, 64 * nbl_l, rlemax, imtf)
+    cmap_d = context_map(b, rng, ntd, 4 * nbl_d, rlemax, imtf, dmap)
+    used_d = set()
     for _ in range(ntl):
         simple_code(b, sorted(rng.sample(range(256), 2)), 8)
     iac = [176, 177, 178, 179]  # cell 2 (explicit distance): insert code 6, copy codes 0 .. 3 = copy lengths 2 .. 5
@@ -785,6 +873,7 @@ def many_trees_stream(seed, ntl, ntd, nbl_l, nbl_d, n_cmds=400, wbits=18):
             break
         tick(D)
         t = dtrees[cmap_d[4 * D["cur"] + min(cpy - 2, 3)]]
+        used_d.add((min(cpy - 2, 3), cmap_d[4 * D["cur"] + min(cpy - 2, 3)]))
         hcode = t[1] - 16
         nbits = 1 + (hcode >> 1)
         base = ((2 + (hcode & 1)) << nbits) - 4 + 1
@@ -801,6 +890,8 @@ def many_trees_stream(seed, ntl, ntd, nbl_l, nbl_d, n_cmds=400, wbits=18):
             dist = base + x
             ring = [dist] + ring[:3]
         pos += cpy
+    if info is not None:
+        info.update(mode=mode, cmap_l=cmap_l, cmap_d=cmap_d, dist_ctx_trees=used_d)
     return b.bytes()
 
 

@@ -13,7 +13,11 @@ STATUS_OUTPUT_TOO_SMALL = 25
 class Stats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in (
         "meta_blocks", "commands", "literals", "raw_bytes", "copies", "copy_bytes", "overlapped_copies",
-        "dict_refs", "dict_bytes", "block_switches", "bits_consumed", "max_distance")]
+        "dict_refs", "dict_bytes", "block_switches", "bits_consumed", "max_distance",
+        "wbits", "metadata_blocks", "mnibbles_mask", "max_block_types", "npostfix_mask", "ndirect_mask", "ntrees_l_mask", "ntrees_d_mask",
+        "cmap_rle", "cmap_imtf", "single_codes", "max_insert_extra", "max_copy_len", "copy_len_lo", "implicit_dist0",
+        "dist_code_mask", "dist_ctx_mask", "dist_ctx_trees", "short_dist_mask", "dist_eq_len", "dist_gt_len", "dist_at_max",
+        "dict_len_mask", "xform_lo", "xform_hi", "raw_blocks", "empty_last")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -38,6 +42,8 @@ def lib():
         L.bro_decode.restype = ctypes.c_int
         L.bro_decode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                  ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint, ctypes.POINTER(Stats)]
+        L.bro_decode_codes.restype = ctypes.c_int
+        L.bro_decode_codes.argtypes = L.bro_decode.argtypes + [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
         L.bro_status_str.restype = ctypes.c_char_p
         L.bro_status_str.argtypes = [ctypes.c_int]
         L.bro_transform.restype = ctypes.c_int
@@ -79,6 +85,19 @@ def decode_at(data: bytes, cap: int, flags: int = 0):
     n = ctypes.c_size_t(0)
     rc = lib().bro_decode(data, len(data), buf, cap, ctypes.byref(n), flags, None)
     return rc, int(n.value), buf.raw[:min(n.value, cap)]
+
+
+def prefix_codes(data: bytes, cap: int = 1 << 16):
+    """The prefix codes of the three command categories of every compressed meta-block the oracle gets through, in stream order:
+    [(meta-block index, category 0 literal / 1 insert&copy / 2 distance, symbols with a codeword)]."""
+    buf = ctypes.create_string_buffer(max(cap, 1))
+    n, k, room = ctypes.c_size_t(0), ctypes.c_size_t(0), 2048
+    while True:
+        codes = (ctypes.c_uint32 * room)()
+        lib().bro_decode_codes(data, len(data), buf, cap, ctypes.byref(n), 0, None, codes, room, ctypes.byref(k))
+        if k.value <= room:
+            return [(c >> 12, (c >> 10) & 3, c & 1023) for c in codes[:k.value]]
+        room = k.value
 
 
 def status_str(code: int) -> str:
