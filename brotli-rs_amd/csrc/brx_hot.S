@@ -4,7 +4,7 @@
 // context-modelled literals, distance symbol / last-distance ring, window copy, dictionary word.  One wavefront = one
 // stream; all decoder state is wave-uniform (SGPRs for what steers control flow, "uniform VGPRs" -- the same value in
 // every lane -- for the bit window and the arithmetic, see TAKE below); the 64 lanes are used as (a) a 256-byte staging
-// buffer of the compressed input (v_readlane feeds the 64-bit bit window), (b) comparators of the canonical prefix-code
+// buffer of the compressed input (v_readlane feeds the bit window: a pair of its dwords), (b) comparators of the canonical prefix-code
 // lookup (lane L holds the left-aligned exclusive upper bound of the length-L codes: one v_cmp + s_ff1 = code length),
 // (c) byte movers AND a queue of copies in flight: a copy of <= 64 bytes takes the next free lanes of ONE pending
 // register (its load is issued under an EXEC mask of just those lanes), so several back-references -- far ones read
@@ -79,12 +79,23 @@
 #define INP s[42:43]
 #define WENDM1 s44
 #define WSAFE s45
-// The loop has no end-of-input test: it is poisoned when the refill pulls in dword WSAFE - 1 = (bitend >> 5) - END_MARGIN - 1
-// (resumable decode; batches: (bitend >> 5) + 3 -- mbw[MBW_WSAFE], set by the dispatcher),
-// the cursor then at most at bitend - 32 * END_MARGIN - 32, and leaves at the next insert&copy symbol or literal run.  Until
-// then it takes at most 24 + 24 (insert / copy extra bits) + 15 + 15 + 24 (a distance block switch: type, count, its extra
-// bits) + 15 + 24 (distance symbol, extra bits) = 141 bits: four dwords would do, five are kept (eight until round 4: a
-// stream's last 36 bytes went through the C++ loop, a third of what a 400-byte stream takes).
+// The loop has no end-of-input test: it is poisoned when the refill pulls in dword d = WSAFE - 1 (mbw[MBW_WSAFE], set by the
+// dispatcher) and leaves at the next insert&copy symbol or literal run.  Until then it takes at most 24 + 24 (insert / copy extra
+// bits) + 15 + 15 + 24 (a distance block switch: type, count, its extra bits) + 15 + 24 (distance symbol, extra bits) = 141 bits.
+// Where the cursor is at that refill (full-chip build; round 7): a refill moves the pair on to dwords (d - 1, d) when a take of
+// n <= 24 bits carries S + n over 32, and leaves S' = S + n - 32 <= 23, so the cursor is 32 (d - 1) + S', in
+// [32 d - 32, 32 d - 9].  (The shifted window of rounds 2 - 6, and of the sparse-launch build still, pulls dword d when fewer than
+// 32 bits are valid: cursor in [32 d - 31, 32 d].  The new cadence pulls a dword at the same cursor or up to 32 bits earlier,
+// never later.)
+//   * Resumable decode: d = (bitend >> 5) - END_MARGIN - 1, cursor <= bitend - 32 END_MARGIN - 32 - 9: at least 32 * 6 + 9 = 201
+//     real bits are left for the 141.  Four dwords would do, five are kept (eight until round 4: a stream's last 36 bytes went
+//     through the C++ loop, a third of what a 400-byte stream takes).
+//   * Batches, last stage: d = (bitend >> 5) + 3, cursor >= 32 (bitend >> 5) + 64 > bitend: a valid stream, whose cursor never
+//     passes bitend, is never poisoned; a stream that runs on leaves with its cursor BEHIND the real end, which is what the
+//     dispatcher tests.  The staged input repeats the stream's last dword beyond its end, so what is pulled early is memory-safe.
+//   * Batches, first stage (the checkpoint, BRX_SPEC_CK_DWORDS = 64 in front of the end): cursor <= 32 (w_end - 65) - 9, and with
+//     the 141 bits the loop parks at least 32 * 60 bits in front of the end: everything consumed up to the checkpoint is real.
+//     The distance needs no change for the new cadence (it was sized against the exit, not against the refill).
 #ifndef END_MARGIN
 #define END_MARGIN 5
 #endif
@@ -115,7 +126,11 @@
 #define WINLO s62
 #define WINHI s63
 #define MBEND s69
-#define SNAV s70
+#ifdef BRX_WIN_SGPR
+#define SNAV s70                // valid bits of the window - 32
+#else
+#define SWC s70                 // S - 32, S = bits consumed from the dword pair VWLO / VWHI (0 .. 31)
+#endif
 #define DCTX s94
 #define HISYM s71
 #define MA2 s71                  // (after the entry code) MA >> 2
@@ -204,13 +219,10 @@
 #define VINFO v29
 #define VC v30
 #define VH v31
-#define VWIN v[32:33]
-#define VWINLO v32
-#define VWINHI v33
+#define VWINLO v32              // the next 32 bits of the stream (the view every lookup and extra-bit field reads)
 #define VI v35
-#define VRF v[36:37]
-#define VRFLO v36
-#define VRFHI v37
+#define VWLO v36                // the dword pair under the view: staged input dwords WL - 2 and WL - 1, unshifted
+#define VWHI v37
 #define VLIT v[38:39]
 #define VLITL v38
 #define VLITB v39
@@ -251,15 +263,19 @@
 #define BRX_DIST_RESIDENT
 #endif
 
-// The bit window (a VGPR pair with the same value in every lane, or an SGPR pair: see TAKE); bits are taken from its low end; SNAV =
-// number of valid bits (>= 32 after a REFILL_CHECK).  A lone wave pays ~4.2 cycles per instruction, ~10 per scalar
+// The bit window.  Full-chip build: two uniform VGPRs hold input dwords WL - 2 and WL - 1 of the staging AS THEY ARE (VWLO, VWHI),
+// SWC = S - 32 counts the bits consumed from that pair (S = 0 .. 31), and VWINLO = the next 32 bits of the stream, always 32 valid
+// ones, is ONE v_alignbit_b32 of the pair behind every take: nothing is shifted along, a refill is two moves.  Sparse-launch
+// build: an SGPR pair shifted along, bits taken from its low end, SNAV = number of valid bits - 32.  A lone wave pays ~4.2 cycles per instruction, ~10 per scalar
 // conditional branch that falls through, ~21-25 per taken branch, ~24 for a v_cmp + s_cbranch_vccnz pair, ~50 per LDS /
 // scalar-cache round trip, ~16 when a SALU instruction consumes an SGPR a VALU instruction wrote (tools/ubench/issue.hip).
 // Sixteen waves on a CU additionally share its scalar ALU (1 instruction per cycle for all of them), the port for
 // SGPR-writing VALU instructions (v_cmp, v_readlane: ~1 per cycle) and the branch unit (~0.6 per cycle)
 // (tools/ubench/power.hip): on a full chip the scalar instruction count of a command is what bounds it.
-// Refill discipline: >= 32 valid bits at .Lcmd; an insert&copy symbol (<= 15) leaves >= 17, enough for a literal or a
-// distance symbol (<= 15); every literal, every extra-bit field > 0 and the distance symbol are followed by a check.
+// Refill discipline: every take is its own check (the carry of SWC / the borrow of SNAV), so every reader finds what it needs:
+// 32 valid bits in VWINLO at any time (full-chip build); >= 32 valid bits at .Lcmd, >= 17 behind an insert&copy symbol (<= 15
+// bits), enough for a literal or a distance symbol (sparse-launch build).  What the primitives cost on the chip:
+// tools/ubench/window.hip, profiles/r07_window_ubench.txt.
 // (bring-up, -DBRX_PROF: cycles spent waiting for copies in flight, and how often, go to Lds::pad[10..13])
 #ifdef BRX_PROF
 #define LDS_PAD LDS_PAD0
@@ -292,8 +308,9 @@
 // Two builds of this file (tools/ubench/power.hip has the measurements behind the choice): a CU has ONE scalar ALU for
 // all of its waves (1 instruction per cycle), while its four SIMDs retire two uniform VALU instructions per cycle
 // between them.  With 16 streams on a CU the scalar ALU is the busiest unit, so the default build keeps the window
-// arithmetic on the vector side; with few waves per CU nothing is contended and the shortest dependent chain wins:
-// -DBRX_WIN_SGPR keeps the window in SGPRs (no VGPR -> SGPR hand-overs for the extra-bit fields, a shorter refill).
+// arithmetic on the vector side (since round 7 as a fixed dword pair and a view, see above); with few waves per CU nothing is
+// contended and the shortest dependent chain wins: -DBRX_WIN_SGPR keeps the window in SGPRs and shifts it along (no VGPR -> SGPR
+// hand-overs for the extra-bit fields).
 #ifdef BRX_WIN_SGPR
 #define WSRC WINLO
 .macro TAKE n, rid
@@ -333,11 +350,16 @@
 .endm
 #else
 #define WSRC VWINLO
+// The window is a FIXED pair of input dwords plus a bit offset: nothing is shifted along.  SWC = S - 32; adding a field's width
+// carries exactly when S + n >= 32, i.e. when the pair's low dword is used up (REFILL_CORE moves the pair on one dword and
+// takes 32 off); the view is then one v_alignbit_b32, whose shift is the low five bits of SWC = S.  Both paths converge on
+// the view behind the return label.  A field is at most 24 bits and S <= 31: one refill always suffices; a take of 0 bits
+// (one-symbol trees, empty extra-bit fields) never carries.
 .macro TAKE n, rid
-    v_lshrrev_b64 VWIN, \n, VWIN
-    s_sub_u32 SNAV, SNAV, \n                             // borrow = fewer than 32 valid bits left
+    s_add_u32 SWC, SWC, \n                               // carry = the pair's low dword is used up
     s_cbranch_scc1 .Lrf_stub_\rid
 .Lrf_back_\rid:
+    v_alignbit_b32 VWINLO, VWHI, VWLO, SWC
 .endm
 .macro TAKE_EXTRA dst, base, n, rid, mul=0                // (\mul: an SGPR with the factor of the extra bits, \base then a VGPR)
     v_bfe_u32 VEX, VWINLO, 0, \n
@@ -349,25 +371,49 @@
     TAKE \n, \rid
     v_readfirstlane_b32 \dst, VEX
 .endm
+// the pair moves on one dword: the next dword of the staged input (lane WL of chunk A) becomes its high half; leaves the
+// WL == WLSTOP test in SCC.  (The two instructions between the v_readlane and the v_mov that reads its SGPR are the two wait
+// states gfx940+ wants there.)
 .macro REFILL_CORE
     v_readlane_b32 T0, VCHA, WL
-    v_mov_b32 VRFHI, 0
-    s_nop 1                                             // gfx940+: VALU-written SGPR read by a VALU: 2 wait states
-    v_mov_b32 VRFLO, T0
-    s_add_u32 SNAV, SNAV, 32                            // (= the number of valid bits before this dword)
-    v_lshlrev_b64 VRF, SNAV, VRF
-    v_or_b32 VWINLO, VWINLO, VRFLO
-    v_or_b32 VWINHI, VWINHI, VRFHI
+    v_mov_b32 VWLO, VWHI
+    s_sub_u32 SWC, SWC, 32
     s_add_u32 WL, WL, 1
+    v_mov_b32 VWHI, T0
     s_cmp_lg_u32 WL, WLSTOP
 .endm
-.macro WIN_INIT lo, hi
-    v_mov_b32 VWINLO, \lo
-    v_mov_b32 VWINHI, \hi
+.macro WIN_INIT lo, hi                                  // at entry: the first two dwords as they are; SWC is set
+    v_mov_b32 VWLO, \lo
+    v_mov_b32 VWHI, \hi
+    v_alignbit_b32 VWINLO, VWHI, VWLO, SWC
 .endm
 .macro WIN_ROLLED
 .endm
 #endif
+// Five dwords of never-executed padding behind every out-of-line refill of the full-chip build (-DSTUB_PAD_NOPS=n: n dwords).
+// The refill of round 7 is 20 bytes shorter than the one before it, and 21 of them moved everything behind them -- the later
+// parts of this loop, its exit code and the compiled segments that follow the statement -- by up to 420 bytes: alice29 and lcet10
+// the same, but 64 x 1 KiB meta-blocks +1.6 % and 16 384 x monkey +1.7 % SLOWER, both beyond their spread.  With the padding every
+// instruction outside the stubs sits where it sat before and both are back inside it (profiles/r07_window_ab.txt, arms `pad` and
+// `new`).  Which of the moved addresses it is that matters: -DTAIL_PAD_NOPS=n puts n dead dwords in ONE place instead, in front
+// of the exit code (.Lx_dist_unfit), so that with STUB_PAD_NOPS=0 TAIL_PAD_NOPS=105 only the exit code and what follows the
+// statement keep their addresses; profiles/r07_window_ab.txt, arm `tail`, has what that measured.  Whoever changes the size of a
+// stub, or of anything else out of line in front of .Lexit, changes those addresses: re-run that A/B (tools/gpu_ab_plain.sh on
+// flush1k_textx4096 and monkeyx16384).  The sparse-launch build (SL_RF_STUB, REFILL_CORE in SGPRs) is unchanged byte for byte and
+// needs no padding: STUB_PAD expands to nothing there.
+#ifndef STUB_PAD_NOPS
+#define STUB_PAD_NOPS 5
+#endif
+#ifndef TAIL_PAD_NOPS
+#define TAIL_PAD_NOPS 0
+#endif
+.macro STUB_PAD
+#ifndef BRX_WIN_SGPR
+    .rept STUB_PAD_NOPS
+    s_nop 0
+    .endr
+#endif
+.endm
 // Out-of-line part of a refill: next dword of the staged input (lane WL of chunk A) enters the window.
 .macro REFILL_STUB id
 .Lrf_stub_\id:
@@ -375,6 +421,7 @@
     s_cbranch_scc1 .Lrf_back_\id
     s_call_b64 LINKA, .Lspecial
     s_branch .Lrf_back_\id
+    STUB_PAD
 .endm
 // A register-resident tree keeps its limits as COUNTS -- lane L: limit[L] in units of L-bit codes (first_code + count), the
 // header word >> (31 - L) -- so that its compare works on the candidate index the lane computes anyway (the top L bits of
@@ -867,8 +914,12 @@
     s_waitcnt vmcnt(0)
     v_readlane_b32 s36, VCHA, 0
     v_readlane_b32 s37, VCHA, 1
+#ifdef BRX_WIN_SGPR
     s_lshr_b64 s[36:37], s[36:37], T3
     s_sub_u32 SNAV, 32, T3                              // SNAV = valid bits - 32 (TAKE)
+#else
+    s_sub_u32 SWC, T3, 32                               // SWC = bits consumed from the pair - 32 (TAKE)
+#endif
     WIN_INIT s36, s37
     s_mov_b32 WL, 2
     s_sub_u32 T0, WSAFE, CBASE
@@ -1210,6 +1261,7 @@
     s_mov_b32 RUN, 0
     s_call_b64 LINKA, .Lspecial
     s_branch .Lrf_back_\id
+    STUB_PAD
 .endm
 
 .macro LIT_RUN_FAST_STUB id, general_id
@@ -1222,6 +1274,7 @@
     s_mov_b32 RUN, 0
     s_call_b64 LINKA, .Lspecial
     s_branch .Lrf_back_\general_id
+    STUB_PAD
 .endm
 
 // (LAND_BODY: see "helpers" below, .Lland)
@@ -1473,6 +1526,7 @@
     s_mov_b32 RUN, 0
     s_call_b64 LINKA, .Lspecial
     s_branch .Lrf_back_\back_id
+    STUB_PAD
 .endm
 .macro LIT_RUN_TAIL_FAST
     s_mov_b32 PBASE, POS
@@ -2761,8 +2815,17 @@
 #endif
 
 // ======================================================================================================== exits
+#ifndef BRX_WIN_SGPR
+    .rept TAIL_PAD_NOPS                                 // (never executed: an unconditional branch ends the code in front of it)
+    s_nop 0
+    .endr
+#endif
 .Lx_dist_unfit:                                         // back to R1 with the literals done: the C++ side reads the distance
+#ifdef BRX_WIN_SGPR
     s_add_u32 SNAV, SNAV, CLEN                          // (un-take the symbol: the bit cursor is derived from SNAV)
+#else
+    s_sub_u32 SWC, SWC, CLEN                            // (un-take the symbol: only the bit cursor is derived from SWC from here on)
+#endif
     s_add_u32 DBLEN, DBLEN, 1
     s_mov_b32 INS, 0
     s_branch .Lexit
@@ -2801,11 +2864,17 @@
     s_bitcmp1_b32 FLAGS, 0
     s_cselect_b32 LBLEN, LBLEN_REAL, LBLEN
     s_cselect_b32 IBLEN, IBLEN_REAL, IBLEN
-    // bit cursor: 32 * (CBASE + WL) - NAV
     s_add_u32 T0, CBASE, WL
     s_lshl_b32 T0, T0, 5
+#ifdef BRX_WIN_SGPR
+    // bit cursor: 32 * (CBASE + WL) - NAV
     s_sub_u32 T0, T0, SNAV
     s_sub_u32 T0, T0, 32                                // (SNAV = valid bits - 32)
+#else
+    // bit cursor: 32 * (CBASE + WL - 2) + S = 32 * (CBASE + WL) - 32 + SWC (the pair holds dwords WL - 2 and WL - 1)
+    s_add_u32 T0, T0, SWC
+    s_sub_u32 T0, T0, 32
+#endif
     v_mov_b32 VT0, T0
     v_mov_b32 VT1, 0
     ds_write_b32 VZERO, VT0 offset:LDS_ST+12            // bitpos (st[3], st[4])

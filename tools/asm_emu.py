@@ -453,6 +453,9 @@ class Wave:
             self.cycles += LAT["cross"]
             a = self.ssrc(ops[1])
             self.sset(ops[0][1], (a & -a).bit_length() - 1 if a else MASK32)
+        elif op == "s_flbit_i32_b32":  # leading zeros, -1 for 0
+            a = self.ssrc(ops[1]) & MASK32
+            self.sset(ops[0][1], 32 - a.bit_length() if a else MASK32)
         elif op == "s_ff1_i32_b64":
             a = self.ssrc64(ops[1])
             self.sset(ops[0][1], (a & -a).bit_length() - 1 if a else MASK32)
