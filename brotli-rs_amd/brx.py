@@ -81,6 +81,10 @@ def load_library():
     L.brx_index_batch.restype = ctypes.c_int
     L.brx_index_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    L.brx_index_quoted_batch.restype = ctypes.c_int
+    L.brx_index_quoted_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_uint64, ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -136,7 +140,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_host_alloc", "brx_host_free", "brx_stream_new_bounded", "brx_generate_batch", "brx_compact_batch",
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
-                    "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch"]
+                    "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch"]
 
 
 def status_str(code: int) -> str:
@@ -331,6 +335,42 @@ class Context:
             pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
         self.index_batch_device(*args, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
         return count, pos_off, pos[:total]
+
+    def index_quoted_batch_device(self, delim, quote, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, open_ptr=None, pos_off_ptr=None,
+                                  pos_ptr=None, total=0, hip_stream=None):
+        """brx_index_quoted_batch on raw device pointers: count[i] = bytes equal to `delim` in out[out_off[i] .. + len[i]) with an even
+        number of `quote` bytes of the stream in front of them; open[i] (uint32) = 1 where the stream holds an odd number of quotes;
+        with pos_off / pos also pos[pos_off[i] + k] = offset within stream i of the k-th of them (entries at or beyond `total` are not
+        written)."""
+        rc = self._lib.brx_index_quoted_batch(self._h, delim, quote, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, open_ptr,
+                                              pos_off_ptr, pos_ptr, total, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_index_quoted_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def index_quoted_batch(self, out, out_off, out_len, delim=10, quote=0x22, stream=None, positions=True):
+        """Record boundaries of the decoded streams of a batch that respect quoted fields (RFC 4180), on the device: a `delim` byte
+        counts only where the number of `quote` bytes in front of it in its stream is even.  Arguments as for index_batch.  Returns
+        (count, open, pos_off, pos): count, pos_off and pos as index_batch gives them (int64 device tensors), open an int32 device
+        tensor, 1 where stream i ends inside a quoted field -- or (count, open) with positions=False.  With positions the call reads
+        the grand total back to allocate `pos`, as index_batch does."""
+        import torch
+        n = int(out_len.numel())
+        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass writes every entry)
+        open_ = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)[:n]
+        hs = stream.cuda_stream if stream is not None else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        args = (int(delim), int(quote), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
+        self.index_quoted_batch_device(*args, count.data_ptr(), open_.data_ptr(), hip_stream=hs)
+        if not positions:
+            return count, open_
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ends = torch.cumsum(count, 0)
+            pos_off = ends - count
+            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
+            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
+        self.index_quoted_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
+        return count, open_, pos_off, pos[:total]
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

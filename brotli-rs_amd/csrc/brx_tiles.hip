@@ -1,4 +1,5 @@
-// brx_tiles.hip -- the plan kernel of the tile pass (brx_tiles.h): one workgroup, first launch of brx_digest_batch and brx_index_batch.
+// brx_tiles.hip -- the plan kernel of the tile pass (brx_tiles.h): one workgroup, first launch of brx_digest_batch, brx_index_batch and
+// brx_index_quoted_batch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

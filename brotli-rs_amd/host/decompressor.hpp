@@ -178,5 +178,13 @@ inline void index_batch(brx_ctx *ctx, uint8_t delim, const uint8_t *out, const u
     if (brx_index_batch(ctx, delim, out, out_off, len, n, span, count, pos_off, pos, total, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_index_batch: ") + brx_last_error());
 }
+// The same with RFC 4180 quoting: a `delim` byte is a record delimiter only where the number of `quote` bytes in front of it in its
+// stream is even; open[i] (may be nullptr) = 1 where stream i ends inside a quoted field.  No escape characters, no CR handling.
+inline void index_quoted_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote, const uint8_t *out, const uint64_t *out_off, const uint64_t *len,
+                               uint32_t n, uint64_t span, uint64_t *count, uint32_t *open = nullptr, const uint64_t *pos_off = nullptr,
+                               uint64_t *pos = nullptr, uint64_t total = 0, void *stream = nullptr) {
+    if (brx_index_quoted_batch(ctx, delim, quote, out, out_off, len, n, span, count, open, pos_off, pos, total, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_index_quoted_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

@@ -331,6 +331,36 @@ int brx_index_batch(brx_ctx *ctx, uint8_t delim,
                     const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                     void *hip_stream);
 
+/* ---- record boundaries that respect quoted fields (device memory only) -----------------------------------
+ * The commonest delimited text is CSV (RFC 4180), and there a delimiter inside a quoted field is data: a consumer that splits a
+ * decoded CSV batch at the positions of brx_index_batch tears records.  This pass applies the quoting rule on the device.  Stream i is
+ * s = out[out_off[i] .. out_off[i] + len[i]); let q(j) be the number of bytes equal to `quote` in s[0 .. j).  Then
+ *   s[j] == delim is a RECORD DELIMITER iff q(j) is even (an embedded quote is doubled, so it toggles twice and changes nothing)
+ *   count[i]              = number of record delimiters of stream i                                            for i < n
+ *   pos[pos_off[i] + k]   = offset WITHIN stream i of its k-th record delimiter, ascending in k                 (fill mode)
+ *   open[i]               = q(len[i]) & 1: 1 where the stream ends inside a quoted field (truncated or malformed CSV), else 0
+ * Every stream starts outside quotes, whatever bytes lie in front of it in its slot.  With delim = ',' the same call gives the field
+ * separators outside quotes.
+ * Not in scope: escape characters (backslash dialects: a quote is a quote wherever it stands), delimiters of more than one byte,
+ * and CR handling (for CRLF text the consumer trims the CR in front of a position).
+ * Everything else is as for brx_index_batch: device pointers only; out, out_off, len, n and span as there; count mode (pos_off ==
+ * NULL and pos == NULL; count required) and fill mode (pos_off and pos both given; count may be NULL, and if given it is written as
+ * in count mode; `total` bounds the entries written to pos); hip_stream NULL = the context's own stream and the call returns when
+ * the results are there, otherwise it is enqueued.  `open` (n entries of 32 bits) may be NULL in either mode.  The context's lock is
+ * held to enqueue only.  Scratch (tile prefix sums, one word per tile and one more, two ticket counters) belongs to the context and
+ * is sized from n and span with no length read back; every launch has a region of its own, so calls on different HIP streams of one
+ * context may overlap; a call with a larger n or span than any before synchronises the device once to grow it, and the 17th call
+ * in flight waits on the host for the first.
+ * BRX_ERR_INVALID_ARGUMENT: ctx NULL, delim == quote, out_off or len NULL with n > 0, only one of pos_off / pos, count NULL in count
+ * mode.  n = 0 returns BRX_SUCCESS, no launch.  Count mode is one pass over the bytes and a one-workgroup pass over the tiles, fill
+ * mode a second pass over the bytes plus 8 bytes per record delimiter; no reference counterpart. */
+int brx_index_quoted_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote,
+                           const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                           uint64_t span,
+                           uint64_t *count, uint32_t *open,
+                           const uint64_t *pos_off, uint64_t *pos, uint64_t total,
+                           void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one

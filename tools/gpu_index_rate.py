@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Times brx_index_batch (record boundaries of a decoded batch, on the device) with HIP events, in one run on one batch:
+"""Times brx_index_batch and brx_index_quoted_batch (record boundaries of a decoded batch, on the device; the second with RFC 4180
+quoting, quote = '"') with HIP events, in one run:
 
-  headline  the decoded output of N x alice29 (default 4096) in device memory, delim = '\\n': count mode, fill mode (pos_off from a
-            count-mode call and torch.cumsum, outside the timed window), brx_compact_batch over the same slots (the yardstick for ONE
-            pass over this ragged layout; it also writes what it reads) and brx_digest_batch (CRC-32) over the same slots
-  large     fill mode over one stream of 70 MiB (random bytes: one delimiter in 256)
-  ragged    fill mode over 4096 streams, lengths log-uniform over 1 B .. 4 MiB (fixed seed, random bytes)
+  headline  the decoded output of N x alice29 (default 4096) in device memory, delim = '\\n': count mode and fill mode of both calls
+            (pos_off from a count-mode call and torch.cumsum, outside the timed window), brx_compact_batch over the same slots (the
+            yardstick for ONE pass over this ragged layout; it also writes what it reads) and brx_digest_batch (CRC-32) over the same
+            slots
+  large     the same four modes over one stream of 70 MiB (random bytes: one delimiter and one quote in 256)
+  ragged    the same four modes over 4096 streams, lengths log-uniform over 1 B .. 4 MiB (fixed seed, random bytes)
 
 Every timed call is warmed up first, timed `--reps` times in windows of `--inner` back-to-back calls between two events; the median
 and the spread of the per-call times are printed.  Counts and positions are checked against numpy on the host (not in the timed
@@ -35,6 +37,7 @@ ctx = brx_knobs.context(0)
 stream = torch.cuda.Stream(device=dev)
 lines = []
 NL = 10
+QUOTE = 0x22
 
 
 def say(s):
@@ -60,36 +63,56 @@ def timed(fn):
     return per[len(per) // 2], per[0], per[-1]
 
 
-def index_rates(name, arena, offs, lens, reference, count_mode=True):
-    """Count mode (if asked) and fill mode over one batch; reference(i) -> np positions of stream i (checked on a sample).
-    -> {mode: median ms}"""
+def quoted_reference(s):
+    """-> (positions of the bytes of s equal to NL with an even number of QUOTE bytes in front of them, parity of the quotes)"""
+    is_q = s == QUOTE
+    inside = (np.cumsum(is_q) - is_q) & 1
+    return np.flatnonzero((s == NL) & (inside == 0)), int(is_q.sum() & 1)
+
+
+def index_rates(name, arena, offs, lens, stream_bytes):
+    """Count mode and fill mode of brx_index_batch and of brx_index_quoted_batch over one batch; stream_bytes(i) -> the bytes of
+    stream i as a numpy array (results checked on a sample).  -> {mode: median ms}"""
     n = lens.numel()
     total_bytes = int(lens.sum().item())
     base = (arena.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, arena.numel())
-    count = torch.zeros(n, dtype=torch.int64, device=dev)
-    res = {}
+    res, shown = {}, {}
+    sample = sorted(set(np.linspace(0, n - 1, 16).astype(int).tolist()))
+    for kind in ("index", "quoted"):
+        count = torch.zeros(n, dtype=torch.int64, device=dev)
+        open_ = torch.zeros(n, dtype=torch.int32, device=dev)
 
-    def count_call():
-        ctx.index_batch_device(NL, *base, count.data_ptr(), hip_stream=stream.cuda_stream)
-    count_call()
-    stream.synchronize()
-    if count_mode:
-        res["count"] = timed(count_call)
-    pos_off = torch.cumsum(count, 0) - count
-    entries = int(count.sum().item())
-    pos = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+        def call(count_ptr, open_ptr, *fill):
+            if kind == "index":
+                ctx.index_batch_device(NL, *base, count_ptr, *fill, hip_stream=stream.cuda_stream)
+            else:
+                ctx.index_quoted_batch_device(NL, QUOTE, *base, count_ptr, open_ptr, *fill, hip_stream=stream.cuda_stream)
 
-    def fill_call():
-        ctx.index_batch_device(NL, *base, None, pos_off.data_ptr(), pos.data_ptr(), entries, hip_stream=stream.cuda_stream)
-    res["fill"] = timed(fill_call)
-    h_count, h_off, h_pos = count.cpu().numpy(), pos_off.cpu().numpy(), pos.cpu().numpy()
-    for i in sorted(set(np.linspace(0, n - 1, 16).astype(int).tolist())):
-        want = reference(i)
-        assert h_count[i] == want.size, "%s: count of stream %d differs from numpy" % (name, i)
-        assert (h_pos[h_off[i]:h_off[i] + h_count[i]] == want).all(), "%s: positions of stream %d differ from numpy" % (name, i)
+        def count_call():
+            call(count.data_ptr(), open_.data_ptr())
+        count_call()
+        stream.synchronize()
+        res[kind + " count"] = timed(count_call)
+        pos_off = torch.cumsum(count, 0) - count
+        entries = int(count.sum().item())
+        pos = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+
+        def fill_call():
+            call(None, None, pos_off.data_ptr(), pos.data_ptr(), entries)
+        res[kind + " fill"] = timed(fill_call)
+        h_count, h_open, h_off, h_pos = count.cpu().numpy(), open_.cpu().numpy(), pos_off.cpu().numpy(), pos.cpu().numpy()
+        for i in sample:
+            s = stream_bytes(i)
+            want, want_open = (np.flatnonzero(s == NL), 0) if kind == "index" else quoted_reference(s)
+            assert h_count[i] == want.size, "%s %s: count of stream %d differs from numpy" % (name, kind, i)
+            assert h_open[i] == want_open, "%s %s: open of stream %d differs from numpy" % (name, kind, i)
+            assert (h_pos[h_off[i]:h_off[i] + h_count[i]] == want).all(), "%s %s: positions of stream %d differ from numpy" % (name, kind, i)
+        shown[kind] = entries
     for mode, (med, lo, hi) in res.items():
-        say("%-9s index %-6s  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s   [%d streams, %.1f MB, %d delimiters]"
-            % (name, mode, med, lo, hi, total_bytes / med / 1e6, n, total_bytes / 1e6, entries))
+        say("%-9s %-12s  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s   [%d streams, %.1f MB, %d entries]"
+            % (name, mode, med, lo, hi, total_bytes / med / 1e6, n, total_bytes / 1e6, shown[mode.split()[0]]))
+    for mode in ("count", "fill"):
+        say("%-9s quoted %-5s = %.3f x index %s" % (name, mode, res["quoted " + mode][0] / res["index " + mode][0], mode))
     return {m: v[0] for m, v in res.items()}
 
 
@@ -131,10 +154,10 @@ def digest_call():
 
 digest_ms, lo, hi = timed(digest_call)
 say("headline  digest crc32  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s" % (digest_ms, lo, hi, n * len(text) / digest_ms / 1e6))
-want_text = np.flatnonzero(np.frombuffer(text, dtype=np.uint8) == NL)
-res = index_rates("headline", out, out_off, out_len, lambda i: want_text)
+np_text = np.frombuffer(text, dtype=np.uint8)
+res = index_rates("headline", out, out_off, out_len, lambda i: np_text)
 for mode, ms in res.items():
-    say("headline  index %-6s = %.3f x compact, %.3f x digest" % (mode, ms / compact_ms, ms / digest_ms))
+    say("headline  %-12s = %.3f x compact, %.3f x digest" % (mode, ms / compact_ms, ms / digest_ms))
 del blob, dst
 
 # ---- one large stream ------------------------------------------------------------------------------------------------
@@ -144,7 +167,7 @@ big_n = (70 << 20) + 12345
 arena = torch.randint(0, 256, (big_n + 64,), dtype=torch.uint8, device=dev, generator=g)
 host = arena.cpu().numpy()
 index_rates("large", arena, torch.tensor([3], dtype=torch.int64, device=dev), torch.tensor([big_n], dtype=torch.int64, device=dev),
-            lambda i: np.flatnonzero(host[3:3 + big_n] == NL), count_mode=False)
+            lambda i: host[3:3 + big_n])
 
 # ---- 4096 log-uniform lengths -------------------------------------------------------------------------------------------
 rng = np.random.default_rng(1234)
@@ -157,7 +180,7 @@ g.manual_seed(99)
 arena = torch.randint(0, 256, (int(h_offs[-1] + slots[-1]),), dtype=torch.uint8, device=dev, generator=g)
 host = arena.cpu().numpy()
 index_rates("ragged", arena, torch.from_numpy(h_offs).to(dev), torch.from_numpy(h_lens).to(dev),
-            lambda i: np.flatnonzero(host[h_offs[i]:h_offs[i] + h_lens[i]] == NL), count_mode=False)
+            lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]])
 ctx.close()
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
