@@ -85,6 +85,10 @@ def load_library():
     L.brx_index_quoted_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint64, ctypes.c_void_p]
+    L.brx_find_batch.restype = ctypes.c_int
+    L.brx_find_batch.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                 ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -140,7 +144,8 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_host_alloc", "brx_host_free", "brx_stream_new_bounded", "brx_generate_batch", "brx_compact_batch",
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
-                    "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch"]
+                    "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
+                    "brx_find_batch"]
 
 
 def status_str(code: int) -> str:
@@ -371,6 +376,41 @@ class Context:
             pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
         self.index_quoted_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
         return count, open_, pos_off, pos[:total]
+
+    def find_batch_device(self, needle, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr=None, pos_ptr=None, total=0,
+                          hip_stream=None):
+        """brx_find_batch on raw device pointers: count[i] = occurrences of `needle` (bytes, 1 .. 16 of them, host memory) in
+        out[out_off[i] .. + len[i]), overlapping ones included; with pos_off / pos also pos[pos_off[i] + k] = offset within stream i of
+        the first byte of the k-th of them (entries at or beyond `total` are not written).  The needle's bytes are taken during the call."""
+        needle = bytes(needle)
+        rc = self._lib.brx_find_batch(self._h, needle, len(needle), out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr,
+                                      pos_ptr, total, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_find_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def find_batch(self, out, out_off, out_len, needle, stream=None, positions=True):
+        """Occurrences of a byte sequence in the decoded streams of a batch, on the device: needle is bytes, 1 .. 16 of them (b"\\r\\n"
+        for CRLF text); every occurrence counts, overlapping ones included.  out, out_off, out_len and stream as for index_batch.
+        Returns (count, pos_off, pos), int64 device tensors: count[i] occurrences in stream i, pos[pos_off[i] + k] the offset within
+        stream i of the first byte of the k-th -- or `count` alone with positions=False.  With positions the call reads the grand
+        total back to allocate `pos`, as index_batch does."""
+        import torch
+        n = int(out_len.numel())
+        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass clears it itself)
+        hs = stream.cuda_stream if stream is not None else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        args = (needle, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
+        self.find_batch_device(*args, count.data_ptr(), hip_stream=hs)
+        if not positions:
+            return count
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ends = torch.cumsum(count, 0)
+            pos_off = ends - count
+            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
+            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
+        self.find_batch_device(*args, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
+        return count, pos_off, pos[:total]
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

@@ -31,6 +31,7 @@
 #include "brx_digest.h"
 #include "brx_index.h"
 #include "brx_index_quoted.h"
+#include "brx_find.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -230,6 +231,8 @@ struct brx_ctx {
     PassRing index_ring;
     // brx_index_quoted_batch (brx_index_quoted.hip): scratch (ticket counters, tile prefix sums, per-tile words)
     PassRing index_quoted_ring;
+    // brx_find_batch (brx_find.hip): scratch (ticket counters, tile prefix sums, per-tile counts)
+    PassRing find_ring;
     std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
     std::vector<uint8_t *> stage_free;
     size_t stage_bytes = 0;
@@ -317,6 +320,7 @@ static void ctx_release(brx_ctx *c) {
     ring_free(c->digest_ring);
     ring_free(c->index_ring);
     ring_free(c->index_quoted_ring);
+    ring_free(c->find_ring);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_in)
@@ -1393,6 +1397,45 @@ extern "C" int brx_index_quoted_batch(brx_ctx *c, uint8_t delim, uint8_t quote, 
                                 c->max_grid / 4u, st);
         HIP_TRY(hipGetLastError());
         if ((rc = ring_record(c->index_quoted_ring, st)) != BRX_SUCCESS) return rc;
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- occurrences of a byte sequence in the decoded streams of a batch (brx_find.hip) ----------------------------------------
+extern "C" int brx_find_batch(brx_ctx *c, const uint8_t *needle, uint32_t needle_len, const uint8_t *out, const uint64_t *out_off,
+                              const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count, const uint64_t *pos_off, uint64_t *pos,
+                              uint64_t total, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: ctx is NULL");
+    if (!needle) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: needle is NULL");
+    if (needle_len == 0 || needle_len > BRX_FIND_MAX_NEEDLE)
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: needle_len is not 1 .. 16");
+    if ((pos_off == nullptr) != (pos == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: pos_off and pos go together");
+    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: count is NULL in count mode");
+    if (n == 0) return BRX_SUCCESS;
+    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: NULL table");
+    // what the scratch of a launch must hold follows from n and span alone: no length is read back
+    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
+    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: span out of range");
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        int rc = ring_reserve(c->find_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
+                              brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                              "find scratch allocation failed");
+        void *scratch = nullptr;
+        if (rc == BRX_SUCCESS) rc = ring_take(c->find_ring, &scratch);
+        if (rc != BRX_SUCCESS) return rc;
+        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU).  The needle's bytes are read here, into
+        // the launch arguments: the caller may reuse its buffer when the call returns.
+        brx_launch_find(out, out_off, len, n, span, needle, needle_len, scratch, max_tiles, count, pos_off, pos, total, c->max_grid / 4u,
+                        st);
+        HIP_TRY(hipGetLastError());
+        if ((rc = ring_record(c->find_ring, st)) != BRX_SUCCESS) return rc;
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;

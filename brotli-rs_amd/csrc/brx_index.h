@@ -1,5 +1,5 @@
 // brx_index.h -- shared by brx_index.hip (kernels) and brx_api.cpp (brx_index_batch): the pass's part of one launch's scratch region;
-// and, for the kernels of brx_index.hip and brx_index_quoted.hip, how a row is loaded and matched.
+// and, for the kernels of brx_index.hip, brx_index_quoted.hip and brx_find.hip, how a row is loaded and matched.
 #pragma once
 #include <stdint.h>
 
@@ -18,7 +18,10 @@ void brx_launch_index(const void *out, const uint64_t *out_off, const uint64_t *
                       unsigned workgroups, void *hip_stream);
 
 #ifdef __HIPCC__
-// ---- what a row is matched with, shared by brx_index.hip and brx_index_quoted.hip ----
+// brx_index.hip, one workgroup of 1024: tile_cnt[0 .. tiles of the batch) -> its exclusive prefix sum, in place (also launched by brx_find.hip)
+__global__ void brx_index_scan_kernel(uint32_t n, const uint64_t *__restrict__ pre, uint64_t max_tiles, uint64_t *__restrict__ tile_cnt);
+
+// ---- what a row is matched with, shared by brx_index.hip, brx_index_quoted.hip and brx_find.hip ----
 // 0x80 in every byte of w that equals the delimiter (d4 = the delimiter in all four bytes).  x = w ^ d4 has a zero byte there; the sum
 // of a byte's low seven bits and 0x7F carries into bit 7 exactly when they are not all zero and never into the next byte, so the test
 // is exact for every byte value, 0x00, 0x80 and 0xFF included.

@@ -1,5 +1,5 @@
 // brx_tiles.h -- the tile pass: the one shape of every pass that walks the decoded streams of a device-resident batch (brx_digest.hip,
-// brx_index.hip, brx_index_quoted.hip; the host side of its scratch in brx_api.cpp).
+// brx_index.hip, brx_index_quoted.hip, brx_find.hip; the host side of its scratch in brx_api.cpp).
 //
 // A work item is one (stream, tile) pair, a tile = 64 KiB of the stream's 1 KiB aligned address range.  The host never learns a length,
 // so a one-workgroup plan kernel (brx_tiles.hip) computes tiles per stream and their exclusive prefix sum pre[0 .. n] on the device.

@@ -186,5 +186,13 @@ inline void index_quoted_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote, const
     if (brx_index_quoted_batch(ctx, delim, quote, out, out_off, len, n, span, count, open, pos_off, pos, total, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_index_quoted_batch: ") + brx_last_error());
 }
+// Occurrences of a byte sequence (`needle`, HOST memory, 1 .. 16 bytes, e.g. "\r\n") in the same batch: count[i] = occurrences in
+// stream i, overlapping ones included; with `pos_off` and `pos` also the offset within the stream of each one's first byte, ascending.
+inline void find_batch(brx_ctx *ctx, const uint8_t *needle, uint32_t needle_len, const uint8_t *out, const uint64_t *out_off,
+                       const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count, const uint64_t *pos_off = nullptr,
+                       uint64_t *pos = nullptr, uint64_t total = 0, void *stream = nullptr) {
+    if (brx_find_batch(ctx, needle, needle_len, out, out_off, len, n, span, count, pos_off, pos, total, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_find_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

@@ -361,6 +361,43 @@ int brx_index_quoted_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote,
                            const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                            void *hip_stream);
 
+/* ---- occurrences of a byte sequence in the decoded bytes of a batch (device memory only) -----------------
+ * Much delimited text does not end its records with one byte: CRLF text ("\r\n", a lone "\n" is data), blank-line separated records
+ * ("\n\n"), HTTP, WARC and MIME header blocks ("\r\n\r\n"), markup terminators ("</doc>\n"), multi-byte UTF-8 separators (U+2028 is
+ * e2 80 a8).  This pass finds a byte sequence, the needle p[0 .. m) with m = needle_len, 1 <= m <= 16.  Stream i is
+ * s = out[out_off[i] .. out_off[i] + len[i]).
+ *   an OCCURRENCE is an offset j with j + m <= len[i] and s[j + k] == p[k] for all k < m
+ *   count[i]              = number of occurrences in stream i                                                    for i < n
+ *   pos[pos_off[i] + k]   = offset WITHIN stream i of the first byte of its k-th occurrence, ascending in k      (fill mode)
+ * ALL occurrences are reported, overlapping ones included: "aa" in "aaa" occurs at 0 and 1.  For a needle that does not overlap
+ * itself ("\r\n", "</doc>") these are exactly the non-overlapping ones; for one that does ("\n\n") the consumer takes every
+ * occurrence that starts at least m behind the one it took last.  No byte outside the stream ever takes part in a match: not the
+ * bytes in front of it in its slot, not the slack behind it, not a neighbouring stream that starts where this one ends.  A stream
+ * shorter than m has no occurrence.  With m = 1 the results equal those of brx_index_batch(delim = p[0]).
+ * Not in scope: needles longer than 16 bytes, several needles in one call, character classes, case folding, and leftmost
+ * non-overlapping selection on the device.  For quote-aware matching with a multi-byte delimiter use brx_index_quoted_batch and trim.
+ *   needle    HOST memory, whatever the other pointers are: needle_len bytes, read before the call returns (the caller may reuse the
+ *             buffer at once).  They travel to the kernels as launch arguments -- no upload, no table, no synchronisation -- so the
+ *             call stays enqueue-only on a caller's stream.
+ * Everything else is as for brx_index_batch: out, out_off, len, count, pos_off and pos are DEVICE pointers; out, out_off, len, n and
+ * span as there (nothing at or beyond out + span, or in front of out, is ever loaded); count mode (pos_off == NULL and pos == NULL;
+ * count required) and fill mode (pos_off and pos both given; count may be NULL, and if given it is written as in count mode; `total`
+ * bounds the entries written to pos); hip_stream NULL = the context's own stream and the call returns when the results are there,
+ * otherwise it is enqueued.  The context's lock is held to enqueue only.  Scratch (tile prefix sums, per-tile counts, two ticket
+ * counters) belongs to the context and is sized from n and span with no length read back; every launch has a region of its own (a
+ * ring of 16, separate from the index passes'), so calls on different HIP streams of one context may overlap; a call with a larger n
+ * or span than any before synchronises the device once to grow it, and the 17th call in flight waits on the host for the first.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order: ctx NULL, needle NULL, needle_len 0 or above 16, only one of pos_off / pos, count
+ * NULL in count mode; then n = 0 returns BRX_SUCCESS, no launch; then out_off or len NULL, span out of range.
+ * Count mode is one pass over the bytes (reads sum(len) and 16 bytes more per 64 KiB tile, writes 8 n), fill mode two plus 8 bytes
+ * per occurrence; no reference counterpart. */
+int brx_find_batch(brx_ctx *ctx, const uint8_t *needle, uint32_t needle_len,
+                   const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                   uint64_t span,
+                   uint64_t *count,
+                   const uint64_t *pos_off, uint64_t *pos, uint64_t total,
+                   void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one

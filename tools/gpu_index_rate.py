@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times brx_index_batch and brx_index_quoted_batch (record boundaries of a decoded batch, on the device; the second with RFC 4180
-quoting, quote = '"') with HIP events, in one run:
+"""Times brx_index_batch, brx_index_quoted_batch (record boundaries of a decoded batch, on the device; the second with RFC 4180
+quoting, quote = '"') and brx_find_batch with HIP events, in one run:
 
   headline  the decoded output of N x alice29 (default 4096) in device memory, delim = '\\n': count mode and fill mode of both calls
             (pos_off from a count-mode call and torch.cumsum, outside the timed window), brx_compact_batch over the same slots (the
@@ -8,6 +8,11 @@ quoting, quote = '"') with HIP events, in one run:
             slots
   large     the same four modes over one stream of 70 MiB (random bytes: one delimiter and one quote in 256)
   ragged    the same four modes over 4096 streams, lengths log-uniform over 1 B .. 4 MiB (fixed seed, random bytes)
+
+Behind the four modes of each batch come the find lines: brx_find_batch (occurrences of a byte sequence) with needles of 1, 2, 4 and
+16 bytes that occur in the data -- for alice29 its line feed, its line ending CR LF, "the " and "the Mock Turtle "; for the random
+bytes a line feed, two line feeds, and 4 and 16 bytes taken from the data -- in count mode and fill mode, each with its ratio to the
+brx_index_batch line of the same batch and mode.
 
 Every timed call is warmed up first, timed `--reps` times in windows of `--inner` back-to-back calls between two events; the median
 and the spread of the per-call times are printed.  Counts and positions are checked against numpy on the host (not in the timed
@@ -116,6 +121,51 @@ def index_rates(name, arena, offs, lens, stream_bytes):
     return {m: v[0] for m, v in res.items()}
 
 
+def find_reference(s, needle):
+    """-> offsets of the occurrences of needle in s, overlapping ones included"""
+    m = len(needle)
+    if s.size < m:
+        return np.zeros(0, dtype=np.int64)
+    ok = np.ones(s.size - m + 1, dtype=bool)
+    for k in range(m):
+        ok &= s[k:s.size - m + 1 + k] == needle[k]
+    return np.flatnonzero(ok)
+
+
+def find_rates(name, arena, offs, lens, stream_bytes, needles, index_ms):
+    """Count mode and fill mode of brx_find_batch over one batch for every needle (results checked on a sample); index_ms = what
+    index_rates returned for the same batch: the yardstick of every line."""
+    n = lens.numel()
+    total_bytes = int(lens.sum().item())
+    base = (arena.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, arena.numel())
+    sample = sorted(set(np.linspace(0, n - 1, 16).astype(int).tolist()))
+    for needle in needles:
+        count = torch.zeros(n, dtype=torch.int64, device=dev)
+
+        def count_call():
+            ctx.find_batch_device(needle, *base, count.data_ptr(), hip_stream=stream.cuda_stream)
+        count_call()
+        stream.synchronize()
+        res = {"count": timed(count_call)}
+        pos_off = torch.cumsum(count, 0) - count
+        entries = int(count.sum().item())
+        assert entries > 0, "%s: the needle %r does not occur" % (name, needle)
+        pos = torch.zeros(entries, dtype=torch.int64, device=dev)
+
+        def fill_call():
+            ctx.find_batch_device(needle, *base, None, pos_off.data_ptr(), pos.data_ptr(), entries, hip_stream=stream.cuda_stream)
+        res["fill"] = timed(fill_call)
+        h_count, h_off, h_pos = count.cpu().numpy(), pos_off.cpu().numpy(), pos.cpu().numpy()
+        for i in sample:
+            want = find_reference(stream_bytes(i), needle)
+            assert h_count[i] == want.size, "%s find %r: count of stream %d differs from numpy" % (name, needle, i)
+            assert (h_pos[h_off[i]:h_off[i] + h_count[i]] == want).all(), "%s find %r: positions of stream %d differ from numpy" % (name, needle, i)
+        for mode, (med, lo, hi) in res.items():
+            say("%-9s find m=%-2d %-5s  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s  = %.3f x index %-5s  [%d entries, needle %s]"
+                % (name, len(needle), mode, med, lo, hi, total_bytes / med / 1e6, med / index_ms["index " + mode], mode, entries,
+                   needle.hex()))
+
+
 # ---- headline: N x alice29, decoded on the device -------------------------------------------------------------------------
 n = args.n
 comp = open(os.path.join(ROOT, "tests", "golden", "data", "alice29.txt.compressed"), "rb").read()
@@ -158,6 +208,7 @@ np_text = np.frombuffer(text, dtype=np.uint8)
 res = index_rates("headline", out, out_off, out_len, lambda i: np_text)
 for mode, ms in res.items():
     say("headline  %-12s = %.3f x compact, %.3f x digest" % (mode, ms / compact_ms, ms / digest_ms))
+find_rates("headline", out, out_off, out_len, lambda i: np_text, (b"\n", b"\r\n", b"the ", b"the Mock Turtle "), res)
 del blob, dst
 
 # ---- one large stream ------------------------------------------------------------------------------------------------
@@ -166,8 +217,10 @@ g.manual_seed(7)
 big_n = (70 << 20) + 12345
 arena = torch.randint(0, 256, (big_n + 64,), dtype=torch.uint8, device=dev, generator=g)
 host = arena.cpu().numpy()
-index_rates("large", arena, torch.tensor([3], dtype=torch.int64, device=dev), torch.tensor([big_n], dtype=torch.int64, device=dev),
-            lambda i: host[3:3 + big_n])
+big_off, big_len = torch.tensor([3], dtype=torch.int64, device=dev), torch.tensor([big_n], dtype=torch.int64, device=dev)
+res = index_rates("large", arena, big_off, big_len, lambda i: host[3:3 + big_n])
+find_rates("large", arena, big_off, big_len, lambda i: host[3:3 + big_n],
+           (b"\n", b"\n\n", host[100000:100004].tobytes(), host[200000:200016].tobytes()), res)
 
 # ---- 4096 log-uniform lengths -------------------------------------------------------------------------------------------
 rng = np.random.default_rng(1234)
@@ -179,8 +232,12 @@ np.cumsum(slots[:-1], out=h_offs[1:])
 g.manual_seed(99)
 arena = torch.randint(0, 256, (int(h_offs[-1] + slots[-1]),), dtype=torch.uint8, device=dev, generator=g)
 host = arena.cpu().numpy()
-index_rates("ragged", arena, torch.from_numpy(h_offs).to(dev), torch.from_numpy(h_lens).to(dev),
-            lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]])
+d_offs, d_lens = torch.from_numpy(h_offs).to(dev), torch.from_numpy(h_lens).to(dev)
+big = int(np.argmax(h_lens))  # (the 4- and 16-byte needles are bytes of the longest stream)
+res = index_rates("ragged", arena, d_offs, d_lens, lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]])
+find_rates("ragged", arena, d_offs, d_lens, lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]],
+           (b"\n", b"\n\n", host[h_offs[big] + 1000:h_offs[big] + 1004].tobytes(), host[h_offs[big] + 2000:h_offs[big] + 2016].tobytes()),
+           res)
 ctx.close()
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
