@@ -25,6 +25,7 @@ OUTPUT_TOO_SMALL = 25
 REF_PANIC = 26
 
 DIGEST_KINDS = {"crc32": 1, "crc32c": 2}  # BRX_DIGEST_*
+INDEX_NO_QUOTE = 1  # BRX_INDEX_NO_QUOTE
 
 
 class BrxError(RuntimeError):
@@ -85,6 +86,10 @@ def load_library():
     L.brx_index_quoted_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint64, ctypes.c_void_p]
+    L.brx_index_escaped_batch.restype = ctypes.c_int
+    L.brx_index_escaped_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
     L.brx_find_batch.restype = ctypes.c_int
     L.brx_find_batch.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
@@ -145,7 +150,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
-                    "brx_find_batch"]
+                    "brx_find_batch", "brx_index_escaped_batch"]
 
 
 def status_str(code: int) -> str:
@@ -375,6 +380,46 @@ class Context:
             total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
             pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
         self.index_quoted_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
+        return count, open_, pos_off, pos[:total]
+
+    def index_escaped_batch_device(self, delim, quote, escape, flags, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, open_ptr=None,
+                                   pos_off_ptr=None, pos_ptr=None, total=0, hip_stream=None):
+        """brx_index_escaped_batch on raw device pointers: a byte of out[out_off[i] .. + len[i]) behind an odd run of `escape` bytes is
+        data; count[i] = bytes equal to `delim` that are not escaped and have an even number of unescaped `quote` bytes of the stream
+        in front of them (flags = INDEX_NO_QUOTE: no byte is a quote); open[i] (uint32): bit 0 = the stream ends inside a quoted field,
+        bit 1 = it ends on an escape with nothing to escape; with pos_off / pos also pos[pos_off[i] + k] = offset within stream i of
+        the k-th of them (entries at or beyond `total` are not written)."""
+        rc = self._lib.brx_index_escaped_batch(self._h, delim, quote, escape, flags, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr,
+                                               open_ptr, pos_off_ptr, pos_ptr, total, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_index_escaped_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def index_escaped_batch(self, out, out_off, out_len, delim=10, quote=0x22, escape=0x5C, no_quote=False, stream=None, positions=True):
+        """Record boundaries of the decoded streams of a batch under a dialect with an escape byte (JSON Lines, SQL text dumps, CSV
+        with an escape character), on the device: a byte behind an odd run of `escape` bytes is data; a `delim` byte counts where it
+        is not escaped and the number of unescaped `quote` bytes in front of it in its stream is even.  no_quote: no byte is a quote
+        (`quote` is ignored).  Arguments otherwise as for index_batch.  Returns what index_quoted_batch returns, (count, open, pos_off,
+        pos) or (count, open) with positions=False; open has two bits: 1 = stream i ends inside a quoted field, 2 = it ends on an
+        escape that has nothing to escape.  With positions the call reads the grand total back to allocate `pos`, as index_batch
+        does."""
+        import torch
+        n = int(out_len.numel())
+        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass writes every entry)
+        open_ = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)[:n]
+        hs = stream.cuda_stream if stream is not None else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        args = (int(delim), int(quote), int(escape), INDEX_NO_QUOTE if no_quote else 0, out.data_ptr(), out_off.data_ptr(),
+                out_len.data_ptr(), n, int(out.numel()))
+        self.index_escaped_batch_device(*args, count.data_ptr(), open_.data_ptr(), hip_stream=hs)
+        if not positions:
+            return count, open_
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ends = torch.cumsum(count, 0)
+            pos_off = ends - count
+            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
+            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
+        self.index_escaped_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
         return count, open_, pos_off, pos[:total]
 
     def find_batch_device(self, needle, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr=None, pos_ptr=None, total=0,

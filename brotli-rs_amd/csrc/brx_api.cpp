@@ -31,6 +31,7 @@
 #include "brx_digest.h"
 #include "brx_index.h"
 #include "brx_index_quoted.h"
+#include "brx_index_escaped.h"
 #include "brx_find.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
@@ -231,6 +232,8 @@ struct brx_ctx {
     PassRing index_ring;
     // brx_index_quoted_batch (brx_index_quoted.hip): scratch (ticket counters, tile prefix sums, per-tile words)
     PassRing index_quoted_ring;
+    // brx_index_escaped_batch (brx_index_escaped.hip): scratch (ticket counters, tile prefix sums, two words per tile)
+    PassRing index_escaped_ring;
     // brx_find_batch (brx_find.hip): scratch (ticket counters, tile prefix sums, per-tile counts)
     PassRing find_ring;
     std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
@@ -320,6 +323,7 @@ static void ctx_release(brx_ctx *c) {
     ring_free(c->digest_ring);
     ring_free(c->index_ring);
     ring_free(c->index_quoted_ring);
+    ring_free(c->index_escaped_ring);
     ring_free(c->find_ring);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -1397,6 +1401,48 @@ extern "C" int brx_index_quoted_batch(brx_ctx *c, uint8_t delim, uint8_t quote, 
                                 c->max_grid / 4u, st);
         HIP_TRY(hipGetLastError());
         if ((rc = ring_record(c->index_quoted_ring, st)) != BRX_SUCCESS) return rc;
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- record boundaries under a dialect with an escape byte, of the decoded streams of a batch (brx_index_escaped.hip) --------
+extern "C" int brx_index_escaped_batch(brx_ctx *c, uint8_t delim, uint8_t quote, uint8_t escape, uint32_t flags, const uint8_t *out,
+                                       const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count,
+                                       uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint64_t total, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: ctx is NULL");
+    if (flags & ~BRX_INDEX_NO_QUOTE) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: unknown flag bits");
+    if (delim == escape) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: delim and escape are the same byte");
+    if (!(flags & BRX_INDEX_NO_QUOTE) && quote == delim)
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: delim and quote are the same byte");
+    if (!(flags & BRX_INDEX_NO_QUOTE) && quote == escape)
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: quote and escape are the same byte");
+    if ((pos_off == nullptr) != (pos == nullptr))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: pos_off and pos go together");
+    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: count is NULL in count mode");
+    if (n == 0) return BRX_SUCCESS;
+    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: NULL table");
+    // what the scratch of a launch must hold follows from n and span alone: no length is read back
+    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
+    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: span out of range");
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        int rc = ring_reserve(c->index_escaped_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
+                              brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                              "escaped index scratch allocation failed");
+        void *scratch = nullptr;
+        if (rc == BRX_SUCCESS) rc = ring_take(c->index_escaped_ring, &scratch);
+        if (rc != BRX_SUCCESS) return rc;
+        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+        brx_launch_index_escaped(out, out_off, len, n, span, delim, quote, escape, flags, scratch, max_tiles, count, open, pos_off, pos,
+                                 total, c->max_grid / 4u, st);
+        HIP_TRY(hipGetLastError());
+        if ((rc = ring_record(c->index_escaped_ring, st)) != BRX_SUCCESS) return rc;
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;

@@ -1,0 +1,278 @@
+// brx_index_escaped.hip -- brx_index_escaped_batch: the record delimiters of every decoded stream of a batch under a dialect with an
+// escape byte (JSON Lines, SQL text dumps, CSV with an escape character), on the device (layout and state maps: brx_index_escaped.h).
+//
+// A byte is escaped exactly when the run of escape bytes directly in front of it, inside its stream, has odd length; an escaped byte
+// is data.  A quote that is not escaped toggles "inside a quoted field", a delimiter that is neither escaped nor inside is a record
+// delimiter.  So the pass is the tile pass of brx_index_quoted.hip with a second carried bit -- and that bit is no xor-able parity:
+// what a tile does to it depends on the state the tile is entered in, so a tile hands on a map of the four states, and resolve
+// composes the maps in tile order.  Count mode is three launches on the caller's stream, fill mode four:
+//   plan     brx_tiles.hip.
+//   count    a pass over the bytes.  Per tile, walked as if it were entered unescaped and outside quotes: c0 / c1 = unescaped delimiters
+//            at even / odd parity of the tile's active quotes, that parity, the escape bit behind the tile, and what stands behind the
+//            tile's leading run of escape bytes.  Entered escaped, only the status of that one byte changes, so the walk from the other
+//            entry state follows from the word (ie_tile_map, ie_select): the bytes are walked once.
+//   resolve  one workgroup, over all tiles of the batch in order: a scan with the composition of maps gives every tile the state it is
+//            entered in (a stream's first tile is a constant map: segmentation falls out of the composition); G = exclusive prefix sum
+//            of the counts selected by it; per stream count[i] as a difference of G and open[i] from the state behind its last tile.
+//   fill     the count kernel's row body from the tile's real entry state, then the fill of brx_index.hip on the selected mask.
+// Ordering between tiles comes from the kernel boundaries alone: no wave ever waits for a value that another wave of the same launch
+// produces (no chained scan, no look-back), so there is nothing that could spin.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "brx_index_escaped.h"
+
+// bit k: byte k of the chunk equals the byte b4 holds four times
+__device__ __forceinline__ uint32_t ie_mask(uint4 v, uint32_t b4) {
+    return ix_nib(ix_eq(v.x, b4)) | (ix_nib(ix_eq(v.y, b4)) << 4) | (ix_nib(ix_eq(v.z, b4)) << 8) | (ix_nib(ix_eq(v.w, b4)) << 12);
+}
+
+// a byte that is none of delimiter, quote and escape, four times: what ix_chunk puts where the stream is not.  In front of a stream
+// it ends any run and toggles nothing, so the stream starts unescaped and outside quotes; behind it it changes no count.
+__device__ __forceinline__ uint32_t ie_filler(uint32_t delim, uint32_t quote, uint32_t escape) {
+    uint32_t f = 0u;
+    while (f == delim || f == quote || f == escape) f++;
+    return f * 0x01010101u;
+}
+
+// One row.  em, qm = the lane's escape and quote bytes; re, rp = the escape bit and the quote parity in front of the row (wave-uniform,
+// moved on to the row's end).  -> bit k: byte k of the lane's chunk is escaped; in: bit k: an odd number of active quotes in front of
+// and including byte k (a delimiter is no quote, so for the bytes that are looked at the inclusive parity is the exclusive one);
+// some: the lanes whose chunk is not made of escape bytes only.
+// The carry into a lane: a chunk of 16 escape bytes hands the run parity in front of it through unchanged (16 is even), any other
+// chunk hands on the parity of its own trailing run whatever came in.  So it is the trailing-run parity of the nearest lower lane
+// whose chunk is not all escape bytes, or the row's if there is none: two ballots and bit arithmetic, no shuffle chain.  The quote
+// parity then goes as in brx_index_quoted.hip, over the quotes that are not escaped.
+__device__ __forceinline__ uint32_t ie_row(uint32_t em, uint32_t qm, uint32_t lane, uint32_t &re, uint32_t &rp, uint32_t &in,
+                                           uint64_t &some) {
+    const bool mixed = em != 0xFFFFu;
+    const uint32_t trail = (uint32_t)__clz((int)(~em << 16)) & 1u; // length of the run of escape bytes the chunk ends with, mod 2
+    const uint64_t a = __ballot(mixed), t = __ballot(mixed && trail);
+    const uint64_t below = a & ((1ull << lane) - 1ull);
+    const uint32_t c = below ? (uint32_t)(t >> (63 - __clzll((long long)below))) & 1u : re;
+    if (a) re = (uint32_t)(t >> (63 - __clzll((long long)a))) & 1u;
+    some = a;
+    const uint32_t esc = ie_escaped(em, c) & 0xFFFFu;
+    uint32_t x = qm & ~esc;
+    x ^= x << 1;
+    x ^= x << 2;
+    x ^= x << 4;
+    x ^= x << 8;
+    const uint64_t b = __ballot((x >> 15) & 1u);
+    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    const uint32_t carry = (before ^ rp) & 1u;
+    rp ^= (uint32_t)__popcll(b) & 1u;
+    in = (x ^ (0u - carry)) & 0xFFFFu;
+    return esc;
+}
+
+// The state behind the tile's last byte of the stream, at address `end` - 1 in the row at `row` (the last one walked: it always holds
+// that byte): escaped iff that byte is an escape byte that is not escaped itself.  Not the row's carry, which for a stream's last tile
+// has passed the filler behind the stream.
+__device__ __forceinline__ uint32_t ie_exit_escape(uint32_t em, uint32_t esc, uint32_t lane, uint64_t row, uint64_t end) {
+    const uint32_t at = (uint32_t)(end - 1u - row);
+    return __ballot(lane == (at >> 4) && ((em & ~esc) >> (at & 15u) & 1u)) != 0ull ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_escaped_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                                                               const uint64_t *__restrict__ len, uint32_t n,
+                                                                               uint64_t span, uint32_t delim, uint32_t quote,
+                                                                               uint32_t escape, uint32_t quotes,
+                                                                               const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                                                               uint64_t *__restrict__ tile_word,
+                                                                               unsigned long long *ticket) {
+    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles; // (more tiles than `span` allows: a caller's error, nothing is written for them)
+    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
+    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
+    const uint32_t qon = quotes ? 0xFFFFu : 0u, f4 = ie_filler(delim, quotes ? quote : delim, escape);
+    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
+    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
+    while (item < total) {
+        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+        uint32_t all = 0, odd = 0, rp = 0, re = 0, em = 0, esc = 0;
+        uint32_t lead = 4u, rodd = 0; // 4: the leading run of escape bytes has not ended yet
+        uint64_t row = it.t0;
+        for (uint32_t r = 0; r < it.rows; r++) {
+            row = it.t0 + (uint64_t)r * BRX_TP_ROW;
+            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
+            em = ie_mask(v, e4);
+            const uint32_t qm = ie_mask(v, q4) & qon, dm = ie_mask(v, d4);
+            uint32_t in;
+            uint64_t some;
+            esc = ie_row(em, qm, lane, re, rp, in, some);
+            if (lead == 4u && some) { // (uniform) once per tile: the first byte that is no escape byte
+                const uint32_t fl = (uint32_t)__ffsll((long long)some) - 1u;
+                const uint32_t k = (uint32_t)__ffs((int)(~em & 0xFFFFu)) - 1u; // (a lane without one: not the lane that is read)
+                const uint32_t mine = (k & 15u) | ((dm >> (k & 15u) & 1u) << 4) | ((qm >> (k & 15u) & 1u) << 5);
+                const uint32_t got = (uint32_t)__shfl((int)mine, (int)fl);
+                // the chunks and rows in front of it are escape bytes only, an even number: the run's parity is that of the offset
+                rodd = got & 1u;
+                lead = row + 16u * fl + (got & 15u) >= it.e ? BRX_IE_LEAD_ALL : got >> 4; // (filler behind the stream's end is no byte of it)
+            }
+            const uint32_t m = dm & ~esc;
+            all += __popc(m);
+            odd += __popc(m & in);
+        }
+        if (lead == 4u) lead = BRX_IE_LEAD_ALL;
+        const uint32_t x = ie_exit_escape(em, esc, lane, row, it.t1);
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) {
+            all += (uint32_t)__shfl_xor((int)all, k);
+            odd += (uint32_t)__shfl_xor((int)odd, k);
+        }
+        if (lane == 0u)
+            tile_word[item] = (uint64_t)(all - odd) | ((uint64_t)odd << BRX_IE_C0_BITS) | ((uint64_t)rp << BRX_IE_PAR_SHIFT) |
+                              ((uint64_t)x << BRX_IE_X_SHIFT) | ((uint64_t)lead << BRX_IE_LEAD_SHIFT) |
+                              ((uint64_t)rodd << BRX_IE_RODD_SHIFT);
+        item = tp_next(ticket, grid_waves, total, lane);
+    }
+}
+
+// the last i < n with pre[i] <= item (tp_item's search)
+__device__ __forceinline__ uint32_t ie_stream_of(uint64_t item, uint32_t n, const uint64_t *__restrict__ pre) {
+    uint32_t lo_i = 0, hi_i = n;
+    while (hi_i - lo_i > 1u) {
+        const uint32_t mid = lo_i + (hi_i - lo_i) / 2u;
+        if (pre[mid] <= item) lo_i = mid; else hi_i = mid;
+    }
+    return lo_i;
+}
+
+// inclusive scan with ie_compose of one map per thread of a 1024-thread workgroup in `part` (1024 words of LDS), the earlier tile being
+// the left operand: -> the composition of the maps of threads 0 .. t
+__device__ __forceinline__ uint32_t ie_block_scan_1024(uint32_t *part, uint32_t t, uint32_t map) {
+    part[t] = map;
+    __syncthreads();
+    for (uint32_t s = 1; s < 1024u; s <<= 1) {
+        const uint32_t f = t >= s ? part[t - s] : BRX_IE_MAP_IDENTITY;
+        __syncthreads();
+        part[t] = ie_compose(f, part[t]);
+        __syncthreads();
+    }
+    return part[t];
+}
+
+// One workgroup; thread t takes a slice of ceil(total / 1024) tiles, as brx_index_scan_kernel does, and until the last barrier reads
+// and writes the words of its own slice only: what crosses slices goes through the two scans in LDS.
+__global__ __launch_bounds__(1024) void brx_index_escaped_resolve_kernel(uint32_t n, const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                                                         uint64_t *tile_word, uint64_t *tile_exit,
+                                                                         uint64_t *__restrict__ count, uint32_t *__restrict__ open) {
+    __shared__ uint64_t part[1024];
+    __shared__ uint32_t maps[1024];
+    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
+    const uint32_t t = threadIdx.x;
+    const uint64_t per = (total + 1023u) / 1024u;
+    const uint64_t i0 = per * t < total ? per * t : total, i1 = i0 + per < total ? i0 + per : total; // (thread 1023: i1 == total)
+    // 1: the slice's map, tile by tile in order; the scan gives the state in front of the slice (the batch starts in state 0, and its
+    // first tile is a stream's first anyway)
+    const uint32_t s0 = i0 < i1 ? ie_stream_of(i0, n, pre) : 0u;
+    uint32_t si = s0;
+    uint32_t map = BRX_IE_MAP_IDENTITY;
+    for (uint64_t i = i0; i < i1; i++) {
+        while (si + 1u < n && pre[si + 1u] <= i) si++;
+        map = ie_compose(map, ie_tile_map(tile_word[i], pre[si] == i));
+    }
+    ie_block_scan_1024(maps, t, map);
+    uint32_t state = t ? ie_apply(maps[t - 1u], 0u) : 0u;
+    // 2: every tile's entry state, the count it selects and the state behind the tile
+    si = s0;
+    uint64_t sum = 0;
+    for (uint64_t i = i0; i < i1; i++) {
+        while (si + 1u < n && pre[si + 1u] <= i) si++;
+        const uint64_t w = tile_word[i];
+        const int first = pre[si] == i;
+        if (first) state = 0u;
+        const uint64_t c = ie_select(w, state);
+        tile_word[i] = c | ((uint64_t)state << BRX_IE_ENTRY_SHIFT);
+        state = ie_apply(ie_tile_map(w, first), state);
+        tile_exit[i] = state;
+        sum += c;
+    }
+    // 3: G, the exclusive prefix sum of the selected counts over all tiles of the batch, into the word, next to the entry state
+    uint64_t run = tp_block_scan_1024(part, t, sum) - sum;
+    for (uint64_t i = i0; i < i1; i++) {
+        const uint64_t w = tile_word[i];
+        tile_word[i] = run | (w & ~BRX_IE_G_MASK);
+        run += w & BRX_IE_G_MASK;
+    }
+    if (t == 1023u) tile_word[total] = run;
+    __syncthreads();
+    // 4: per stream: count as a difference of G over the whole batch, open from the state behind the stream's last tile; streams
+    // without tiles (which share their successor's pre[]) get 0 and 0
+    for (uint64_t i = t; i < n; i += 1024u) {
+        const uint64_t a = pre[i] < total ? pre[i] : total, b = pre[i + 1u] < total ? pre[i + 1u] : total;
+        if (count) count[i] = (tile_word[b] & BRX_IE_G_MASK) - (tile_word[a] & BRX_IE_G_MASK);
+        if (open) open[i] = b > a ? (uint32_t)tile_exit[b - 1u] : 0u;
+    }
+}
+
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_escaped_fill_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                                                              const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
+                                                                              uint32_t delim, uint32_t quote, uint32_t escape,
+                                                                              uint32_t quotes, const uint64_t *__restrict__ pre,
+                                                                              uint64_t max_tiles, const uint64_t *__restrict__ tile_word,
+                                                                              const uint64_t *__restrict__ pos_off,
+                                                                              uint64_t *__restrict__ pos, uint64_t pos_total,
+                                                                              unsigned long long *ticket) {
+    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
+    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
+    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
+    const uint32_t qon = quotes ? 0xFFFFu : 0u, f4 = ie_filler(delim, quotes ? quote : delim, escape);
+    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
+    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
+    while (item < total) {
+        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+        const uint64_t w = tp_uniform(tile_word[item]);
+        // index in pos of the tile's first record delimiter: the stream's first entry + those of the stream's tiles in front of this one
+        uint64_t base = tp_uniform(pos_off[it.si] + ((w & BRX_IE_G_MASK) - (tile_word[pre[it.si]] & BRX_IE_G_MASK)));
+        uint32_t rp = (uint32_t)(w >> BRX_IE_ENTRY_SHIFT) & 1u, re = (uint32_t)(w >> (BRX_IE_ENTRY_SHIFT + 1u)) & 1u;
+        for (uint32_t r = 0; r < it.rows; r++) {
+            const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
+            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
+            uint32_t in;
+            uint64_t some;
+            const uint32_t esc = ie_row(ie_mask(v, e4), ie_mask(v, q4) & qon, lane, re, rp, in, some); // (every row: it moves the state on)
+            uint32_t m = ie_mask(v, d4) & ~esc & ~in; // bit k: byte k of the chunk is a record delimiter of the stream
+            if (__ballot(m != 0u) == 0ull) continue; // (uniform) a row without one: no position work
+            const uint32_t c = (uint32_t)__popc(m);
+            uint32_t incl = c;
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, s);
+                if (lane >= (uint32_t)s) incl += up;
+            }
+            uint64_t idx = base + (incl - c);
+            const uint64_t rel = row + 16u * lane - it.a; // offset of the chunk's byte 0 in the stream (m == 0 where that is in front of it)
+            while (m) {
+                const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
+                m &= m - 1u;
+                if (idx < pos_total) pos[idx] = rel + k;
+                idx++;
+            }
+            base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+        item = tp_next(ticket, grid_waves, total, lane);
+    }
+}
+
+void brx_launch_index_escaped(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint8_t delim,
+                              uint8_t quote, uint8_t escape, uint32_t flags, void *scratch, uint64_t max_tiles, uint64_t *count,
+                              uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint64_t total, unsigned workgroups,
+                              void *hip_stream) {
+    uint64_t *pre = brx_tp_pre(scratch), *words = (uint64_t *)brx_tp_own(scratch, n), *exits = words + max_tiles + 1u;
+    const uint32_t quotes = (flags & BRX_INDEX_ESCAPED_NO_QUOTE) ? 0u : 1u;
+    hipStream_t st = (hipStream_t)hip_stream;
+    brx_launch_tile_plan(out, out_off, len, n, scratch, nullptr, 0u, st); // (resolve writes every count[i] and open[i]: nothing to clear)
+    hipLaunchKernelGGL(brx_index_escaped_count_kernel, dim3(workgroups), dim3(BRX_TP_WG), 0, st, (const uint8_t *)out, out_off, len, n,
+                       span, (uint32_t)delim, (uint32_t)quote, (uint32_t)escape, quotes, pre, max_tiles, words,
+                       brx_tp_ticket_a(scratch));
+    hipLaunchKernelGGL(brx_index_escaped_resolve_kernel, dim3(1), dim3(1024), 0, st, n, pre, max_tiles, words, exits, count, open);
+    if (!pos) return;
+    hipLaunchKernelGGL(brx_index_escaped_fill_kernel, dim3(workgroups), dim3(BRX_TP_WG), 0, st, (const uint8_t *)out, out_off, len, n,
+                       span, (uint32_t)delim, (uint32_t)quote, (uint32_t)escape, quotes, pre, max_tiles, words, pos_off, pos, total,
+                       brx_tp_ticket_b(scratch));
+}

@@ -186,6 +186,18 @@ inline void index_quoted_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote, const
     if (brx_index_quoted_batch(ctx, delim, quote, out, out_off, len, n, span, count, open, pos_off, pos, total, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_index_quoted_batch: ") + brx_last_error());
 }
+// The same for dialects with an escape byte (JSON Lines, SQL text dumps, CSV with an escape character): a byte behind an odd run of
+// `escape` bytes is data; a `delim` byte is a record delimiter where it is not escaped and the number of unescaped `quote` bytes in
+// front of it is even.  flags = BRX_INDEX_NO_QUOTE: no byte is a quote.  open[i] (may be nullptr): bit 0 = stream i ends inside a
+// quoted field, bit 1 = it ends on an escape that has nothing to escape.
+inline void index_escaped_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote, uint8_t escape, uint32_t flags, const uint8_t *out,
+                                const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count,
+                                uint32_t *open = nullptr, const uint64_t *pos_off = nullptr, uint64_t *pos = nullptr, uint64_t total = 0,
+                                void *stream = nullptr) {
+    if (brx_index_escaped_batch(ctx, delim, quote, escape, flags, out, out_off, len, n, span, count, open, pos_off, pos, total, stream) !=
+        BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_index_escaped_batch: ") + brx_last_error());
+}
 // Occurrences of a byte sequence (`needle`, HOST memory, 1 .. 16 bytes, e.g. "\r\n") in the same batch: count[i] = occurrences in
 // stream i, overlapping ones included; with `pos_off` and `pos` also the offset within the stream of each one's first byte, ascending.
 inline void find_batch(brx_ctx *ctx, const uint8_t *needle, uint32_t needle_len, const uint8_t *out, const uint64_t *out_off,

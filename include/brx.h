@@ -341,8 +341,8 @@ int brx_index_batch(brx_ctx *ctx, uint8_t delim,
  *   open[i]               = q(len[i]) & 1: 1 where the stream ends inside a quoted field (truncated or malformed CSV), else 0
  * Every stream starts outside quotes, whatever bytes lie in front of it in its slot.  With delim = ',' the same call gives the field
  * separators outside quotes.
- * Not in scope: escape characters (backslash dialects: a quote is a quote wherever it stands), delimiters of more than one byte,
- * and CR handling (for CRLF text the consumer trims the CR in front of a position).
+ * Not in scope: escape characters (here a quote is a quote wherever it stands; for backslash dialects see brx_index_escaped_batch
+ * below), delimiters of more than one byte, and CR handling (for CRLF text the consumer trims the CR in front of a position).
  * Everything else is as for brx_index_batch: device pointers only; out, out_off, len, n and span as there; count mode (pos_off ==
  * NULL and pos == NULL; count required) and fill mode (pos_off and pos both given; count may be NULL, and if given it is written as
  * in count mode; `total` bounds the entries written to pos); hip_stream NULL = the context's own stream and the call returns when
@@ -360,6 +360,50 @@ int brx_index_quoted_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote,
                            uint64_t *count, uint32_t *open,
                            const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                            void *hip_stream);
+
+/* ---- record boundaries under a dialect with an escape byte (device memory only) --------------------------
+ * The largest family of delimited text escapes instead of (or on top of) quoting: JSON and JSON Lines write a quote inside a string
+ * as \", PostgreSQL COPY text, MySQL / MariaDB tab dumps and Hive text tables have no quoting at all and put a backslash in front of
+ * a delimiter that is data, and CSV is written with an escape character in place of doubled quotes (Python's escapechar, SQL's ESCAPED
+ * BY).  Split at the positions of brx_index_batch or brx_index_quoted_batch such text tears.  This pass applies the rule on the device.
+ * Stream i is s = out[out_off[i] .. out_off[i] + len[i]); D = delim, Q = quote, E = escape.
+ *   esc(0) = 0 and esc(j + 1) = (s[j] == E && !esc(j)).  Byte j is ESCAPED iff esc(j): equivalently, iff the maximal run of E bytes
+ *       directly in front of it, inside the stream, has odd length.  An escaped byte is data whatever its value, an E included.
+ *   an ACTIVE QUOTE is a byte equal to Q that is not escaped; q(j) is the number of active quotes in s[0 .. j)
+ *   s[j] is a RECORD DELIMITER iff s[j] == D, byte j is not escaped, and q(j) is even.  The escape acts inside and outside quoted
+ *       fields alike; a doubled quote still toggles twice, so RFC 4180 text with an escape dialect on top behaves as expected.
+ *   count[i]              = number of record delimiters of stream i                                            for i < n
+ *   pos[pos_off[i] + k]   = offset WITHIN stream i of its k-th record delimiter, ascending in k                 (fill mode)
+ *   open[i]               = two bits.  bit 0 = q(len[i]) & 1: the stream ends inside a quoted field.  bit 1 = esc(len[i]): the stream
+ *                           ends on an active escape, one that has nothing to escape (truncated text).
+ * Every stream starts unescaped and outside quotes, whatever bytes lie in front of it in its slot, and nothing behind the stream
+ * (slack, a neighbouring stream) takes part: an escape on a stream's last byte does not escape the first byte of the next stream.
+ *   flags     BRX_INDEX_NO_QUOTE: no byte is a quote -- the `quote` argument is ignored and bit 0 of open[i] is 0 -- for the quote-less
+ *             dialects above.  Other bits must be 0.
+ * With delim = ',' the same call gives the field separators; for JSON Lines those are the commas outside strings.
+ * Not in scope: delimiters, quotes or escapes of more than one byte; escapes that act only inside quotes; decoding what an escape
+ * sequence means (\n, \uXXXX); CR handling; several delimiters in one call.
+ * Everything else is as for brx_index_quoted_batch: device pointers only; out, out_off, len, n and span as there (nothing at or beyond
+ * out + span, or in front of out, is ever loaded); count mode (pos_off == NULL and pos == NULL; count required) and fill mode (pos_off
+ * and pos both given; count may be NULL, and if given it is written as in count mode; `total` bounds the entries written to pos);
+ * `open` (n entries of 32 bits) may be NULL in either mode; hip_stream NULL = the context's own stream and the call returns when the
+ * results are there, otherwise it is enqueued.  The context's lock is held to enqueue only.  Scratch (tile prefix sums, two words per
+ * tile and one more, two ticket counters) belongs to the context and is sized from n and span with no length read back; every launch
+ * has a region of its own (a ring of 16, separate from the other passes'), so calls on different HIP streams of one context may
+ * overlap; a call with a larger n or span than any before synchronises the device once to grow it, and the 17th call in flight waits
+ * on the host for the first.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits; delim == escape; without
+ * BRX_INDEX_NO_QUOTE quote == delim or quote == escape; only one of pos_off / pos; count NULL in count mode; then n = 0 returns
+ * BRX_SUCCESS, no launch; then out_off or len NULL, span out of range.
+ * Count mode is one pass over the bytes and a one-workgroup pass over the tiles, fill mode a second pass over the bytes plus 8 bytes
+ * per record delimiter; no reference counterpart. */
+#define BRX_INDEX_NO_QUOTE 1u
+int brx_index_escaped_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote, uint8_t escape, uint32_t flags,
+                            const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                            uint64_t span,
+                            uint64_t *count, uint32_t *open,
+                            const uint64_t *pos_off, uint64_t *pos, uint64_t total,
+                            void *hip_stream);
 
 /* ---- occurrences of a byte sequence in the decoded bytes of a batch (device memory only) -----------------
  * Much delimited text does not end its records with one byte: CRLF text ("\r\n", a lone "\n" is data), blank-line separated records

@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
-"""Times brx_index_batch, brx_index_quoted_batch (record boundaries of a decoded batch, on the device; the second with RFC 4180
-quoting, quote = '"') and brx_find_batch with HIP events, in one run:
+"""Times brx_index_batch, brx_index_quoted_batch, brx_index_escaped_batch (record boundaries of a decoded batch, on the device; the
+second with RFC 4180 quoting, quote = '"'; the third with an escape byte on top, escape = '\\') and brx_find_batch with HIP events,
+in one run:
 
-  headline  the decoded output of N x alice29 (default 4096) in device memory, delim = '\\n': count mode and fill mode of both calls
+  headline  the decoded output of N x alice29 (default 4096) in device memory, delim = '\\n': count mode and fill mode of the three calls
             (pos_off from a count-mode call and torch.cumsum, outside the timed window), brx_compact_batch over the same slots (the
             yardstick for ONE pass over this ragged layout; it also writes what it reads) and brx_digest_batch (CRC-32) over the same
             slots
-  large     the same four modes over one stream of 70 MiB (random bytes: one delimiter and one quote in 256)
-  ragged    the same four modes over 4096 streams, lengths log-uniform over 1 B .. 4 MiB (fixed seed, random bytes)
+  large     the same six modes over one stream of 70 MiB (random bytes: one delimiter and one quote in 256)
+  ragged    the same six modes over 4096 streams, lengths log-uniform over 1 B .. 4 MiB (fixed seed, random bytes)
 
-Behind the four modes of each batch come the find lines: brx_find_batch (occurrences of a byte sequence) with needles of 1, 2, 4 and
+Behind the six modes of each batch (the escaped ones with their ratio to the quoted pass of the same run) come the find lines: brx_find_batch (occurrences of a byte sequence) with needles of 1, 2, 4 and
 16 bytes that occur in the data -- for alice29 its line feed, its line ending CR LF, "the " and "the Mock Turtle "; for the random
 bytes a line feed, two line feeds, and 4 and 16 bytes taken from the data -- in count mode and fill mode, each with its ratio to the
 brx_index_batch line of the same batch and mode.
@@ -29,6 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from brotli_rs_amd import brx  # noqa: E402
 import brx_knobs  # noqa: E402
+import escaped_oracle  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=4096)
@@ -43,6 +45,7 @@ stream = torch.cuda.Stream(device=dev)
 lines = []
 NL = 10
 QUOTE = 0x22
+ESCAPE = 0x5C
 
 
 def say(s):
@@ -76,22 +79,24 @@ def quoted_reference(s):
 
 
 def index_rates(name, arena, offs, lens, stream_bytes):
-    """Count mode and fill mode of brx_index_batch and of brx_index_quoted_batch over one batch; stream_bytes(i) -> the bytes of
+    """Count mode and fill mode of brx_index_batch, brx_index_quoted_batch and brx_index_escaped_batch over one batch; stream_bytes(i) -> the bytes of
     stream i as a numpy array (results checked on a sample).  -> {mode: median ms}"""
     n = lens.numel()
     total_bytes = int(lens.sum().item())
     base = (arena.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, arena.numel())
     res, shown = {}, {}
     sample = sorted(set(np.linspace(0, n - 1, 16).astype(int).tolist()))
-    for kind in ("index", "quoted"):
+    for kind in ("index", "quoted", "escaped"):
         count = torch.zeros(n, dtype=torch.int64, device=dev)
         open_ = torch.zeros(n, dtype=torch.int32, device=dev)
 
         def call(count_ptr, open_ptr, *fill):
             if kind == "index":
                 ctx.index_batch_device(NL, *base, count_ptr, *fill, hip_stream=stream.cuda_stream)
-            else:
+            elif kind == "quoted":
                 ctx.index_quoted_batch_device(NL, QUOTE, *base, count_ptr, open_ptr, *fill, hip_stream=stream.cuda_stream)
+            else:
+                ctx.index_escaped_batch_device(NL, QUOTE, ESCAPE, 0, *base, count_ptr, open_ptr, *fill, hip_stream=stream.cuda_stream)
 
         def count_call():
             call(count.data_ptr(), open_.data_ptr())
@@ -108,7 +113,8 @@ def index_rates(name, arena, offs, lens, stream_bytes):
         h_count, h_open, h_off, h_pos = count.cpu().numpy(), open_.cpu().numpy(), pos_off.cpu().numpy(), pos.cpu().numpy()
         for i in sample:
             s = stream_bytes(i)
-            want, want_open = (np.flatnonzero(s == NL), 0) if kind == "index" else quoted_reference(s)
+            want, want_open = ((np.flatnonzero(s == NL), 0) if kind == "index" else quoted_reference(s) if kind == "quoted" else
+                               escaped_oracle.vec(s, NL, QUOTE, ESCAPE))
             assert h_count[i] == want.size, "%s %s: count of stream %d differs from numpy" % (name, kind, i)
             assert h_open[i] == want_open, "%s %s: open of stream %d differs from numpy" % (name, kind, i)
             assert (h_pos[h_off[i]:h_off[i] + h_count[i]] == want).all(), "%s %s: positions of stream %d differ from numpy" % (name, kind, i)
@@ -118,6 +124,9 @@ def index_rates(name, arena, offs, lens, stream_bytes):
             % (name, mode, med, lo, hi, total_bytes / med / 1e6, n, total_bytes / 1e6, shown[mode.split()[0]]))
     for mode in ("count", "fill"):
         say("%-9s quoted %-5s = %.3f x index %s" % (name, mode, res["quoted " + mode][0] / res["index " + mode][0], mode))
+    for mode in ("count", "fill"):
+        say("%-9s escaped %-5s = %.3f x quoted %s, %.3f x index %s" % (name, mode, res["escaped " + mode][0] / res["quoted " + mode][0], mode,
+                                                                      res["escaped " + mode][0] / res["index " + mode][0], mode))
     return {m: v[0] for m, v in res.items()}
 
 
