@@ -202,7 +202,9 @@
 #define VDHOFF v10
 #define VB4 v11
 #define VPEND v12
+#ifdef BRX_WIN_SGPR
 #define VITAB v23               // lane l: context info of bytes 4l .. 4l+3 under the current context mode (= LDS_ITAB)
+#endif                          // (the full-chip build reads the table in LDS with the pending lanes themselves: LAND_BODY_CTX; v23 is free there)
 #define VDICTINFO v13
 #define VQ v[14:17]
 #define VT0 v18
@@ -827,7 +829,9 @@
 .Lit_not3:
     v_lshlrev_b32 VT0, 2, VLANE
     ds_write_b32 VT0, VT1 offset:LDS_ITAB
+#ifdef BRX_WIN_SGPR
     v_mov_b32 VITAB, VT1                                // (resident copy: LIT_CTX_ENTRY)
+#endif
     // up to 8 literal trees, one context mode: limits and bases live in v70..v85 (pair t = tree t, reached through M0),
     // lane 16 of a tree's limits carries the LDS address of its symbol list.  A one-symbol tree becomes a real table:
     // limit[0] = all ones ("matches" at length 0, no bits), a two-entry list [x, x].
@@ -1292,6 +1296,42 @@
     s_mov_b32 PBASE, POS
     .endif
 .endm
+#ifndef BRX_WIN_SGPR
+// The landing in front of a literal run of the resident loops (full-chip build, LIT_CTX_ENTRY), with the run's first context
+// formed INSIDE its EXEC window, by all pending lanes at once: every lane reads the context info of the byte it lands (the
+// 256-byte table in LDS, addressed by VPEND itself: every writer of VPEND leaves bits 31:8 zero) and splits it into the byte's
+// share as p1 and as p2; one DPP shift by a lane puts the left neighbour's p2 share next to the own p1 share.  Out, lane k:
+// VT2 = context id of a literal that would follow pending byte k, VT3 = byte k's share as the p2 of the literal after that.
+// PFREE can be 63: the loop's 17-lane EXEC would not do.  \v = m3: the fields are those of context mode 3 (both shares are
+// lut2(byte), info bits 4:2); mx: the p1 share is info >> 2 (six bits, no mask), the p2 share info & MB (0 in modes 0 and 1).
+// T4 = PFREE - 1 (the lane LIT_CTX_ENTRY reads) and T0 = ring coordinate of the run are scalar work that fills the two wait
+// states a DPP read wants behind the VALU write of its VGPRs (nothing inserts them inside an asm statement).
+.macro LAND_BODY_CTX v
+    s_add_u32 T6, PBASE, SKEW
+    s_bfm_b64 exec, PFREE, 0
+    v_add_u32 VT1, T6, VLANE
+    v_and_b32 VT1, RMASK, VT1
+    PROF_WAIT_VM
+    s_waitcnt vmcnt(0) lgkmcnt(0)
+    ds_write_b8 VT1, VPEND
+    ds_read_u8 VT0, VPEND offset:LDS_ITAB               // info(byte) under the meta-block's context mode
+    s_waitcnt lgkmcnt(0)
+.ifc \v,m3
+    v_bfe_u32 VT3, VT0, 2, 3                            // lut2(byte): the share as p2 ...
+    v_lshlrev_b32 VT2, 3, VT3                           // ... and as p1
+.else
+    v_and_b32 VT3, MB, VT0
+    v_lshrrev_b32 VT2, 2, VT0
+.endif
+    s_sub_u32 T4, PFREE, 1
+    s_add_u32 T0, POS, SKEW
+    // (PFREE >= 2 whenever it is not 0 -- a copy is at least 2 bytes long, and a ONE-byte transformed word is stored straight to the
+    // ring, .Lxf_upper -- so the lane that is read, PFREE - 1 >= 1, always has a left neighbour; lane 0 has none and keeps its p1 share)
+    v_or_b32_dpp VT2, VT3, VT2 wave_shr:1 row_mask:0xf bank_mask:0xf
+    s_mov_b64 exec, XLOOP
+    s_mov_b32 PFREE, 0
+.endm
+#endif
 // ---- literals (reference parse_insert_literals :1286-1365)
 .Lhave_lits:
     s_sub_u32 MBLEFT, MBEND, POS
@@ -1415,9 +1455,15 @@
 // (.Lhave_lits jumps to .Llit_r_entry_*) pending bytes into the ring, then the context of the first literal straight into the
 // scalar registers of the loop -- .Lland_ctx without the detour through the vector-side form
 // The two bytes in front of a run that follows a copy are the LAST TWO PENDING ones (a copy is at least 2 bytes long, a
-// dictionary word 4): they are read from their lanes of VPEND, and their context info from its lane of VITAB (4 bytes per
-// lane) -- no trip to the ring and none to the info table in front of the run's first literal (two dependent LDS round
-// trips less per run; the landing's store is no longer waited for by anything).  -DBRX_CTX_RING: the bytes from the ring.
+// dictionary word 4).  Sparse-launch build: they are read from their lanes of VPEND, and their context info from its lane of
+// VITAB (4 bytes per lane) -- no trip to the ring and none to the info table in front of the run's first literal (two dependent
+// LDS round trips less per run; the landing's store is no longer waited for by anything): 14 scalar instructions and four
+// v_readlane, the shortest chain for a lone wave.  Full-chip build (round 8): the CU's one scalar ALU is what 16 waves wait for,
+// so the context is formed on the vector side by ALL pending lanes inside the landing's EXEC window (LAND_BODY_CTX: one read of
+// the info table in LDS, two or three VALU instructions, one DPP shift by a lane) and lane PFREE - 1 is read with two v_readlane:
+// 2 scalar instructions, one LDS trip.  Only the ring path (nothing pending) still has info bytes on the scalar side
+// (LIT_CTX_FROM_INFO, out of line there).  tools/ubench/runentry.hip, profiles/r08_run_entry_*.txt.
+// -DBRX_CTX_RING: the bytes from the ring.
 .macro LIT_CTX_RING_BYTES                               // T6 / T7 = context info of the last two bytes of the ring
     v_add_u32 VT0, -1, VPA
     v_add_u32 VT1, -2, VPA
@@ -1442,6 +1488,11 @@
     s_add_u32 T6, POS, SKEW
     v_bfe_u32 VPA, T6, 0, 11
     LIT_CTX_RING_BYTES
+#elif !defined(BRX_WIN_SGPR)
+    LAND_BODY_CTX \v                                    // (PBASE: the run's end sets it, nothing reads it in between)
+    v_bfe_u32 VPA, T0, 0, 11
+    v_readlane_b32 T5, VT3, T4                          // p1's share as a later p2
+    v_readlane_b32 T4, VT2, T4                          // context id of the first literal
 #else
     s_sub_u32 T4, PFREE, 1                              // lanes of the last two pending bytes
     s_sub_u32 T5, PFREE, 2
@@ -1459,13 +1510,18 @@
     s_lshr_b32 T6, T0, T6                               // (bits 8.. are the neighbours' info: only fields of bits 7:0 are taken below)
     s_lshr_b32 T7, T1, T7
 #endif
+#if defined(BRX_CTX_RING) || defined(BRX_WIN_SGPR)
+    LIT_CTX_FROM_INFO \v
+#endif
+.Llit_r_go_\v:
+.endm
+.macro LIT_CTX_FROM_INFO v                              // T6 / T7 = context info of p1 / p2 -> T4, T5
 .Llit_r_ctx_have_\v:
     s_bfe_u32 T1, T6, 0x60002
     s_and_b32 T1, T1, MA2
     s_bfe_u32 T5, T6, BFEBI                             // p1's share as a later p2
     s_bfe_u32 T7, T7, BFEBI
     s_or_b32 T4, T1, T7                                 // context id of the first literal
-.Llit_r_go_\v:
 .endm
 .macro LIT_CTX_ENTRY_AUX v
 #ifndef BRX_CTX_RING
@@ -1473,7 +1529,12 @@
     s_add_u32 T6, POS, SKEW
     v_bfe_u32 VPA, T6, 0, 11
     LIT_CTX_RING_BYTES
+#ifdef BRX_WIN_SGPR
     s_branch .Llit_r_ctx_have_\v
+#else
+    LIT_CTX_FROM_INFO \v                                // (full-chip build: only the ring path has the info bytes on the scalar side)
+    s_branch .Llit_r_go_\v
+#endif
 #endif
 .Llit_r_entry_nopend_\v:
     s_cmp_lt_u32 POS, 2                                 // (a copy is at least 2 bytes long: nothing is pending at the stream's start)
@@ -2405,7 +2466,11 @@
     v_lshlrev_b32 VT1, 3, VT1                           // 8 * (lane - first lane of the prefix)
     s_bfm_b64 exec, T2, PFREE
     v_lshrrev_b64 v[54:55], VT1, s[12:13]
+#ifdef BRX_WIN_SGPR
     v_mov_b32 VPEND, v54                                // prefix bytes
+#else
+    v_and_b32 VPEND, 0xff, v54                          // prefix bytes (bits 31:8 zero: VPEND addresses the info table, LAND_BODY_CTX)
+#endif
     s_add_u32 T4, PFREE, T2                             // first lane of the word's part
     s_add_u32 T0, T0, T5
     s_sub_u32 T0, T0, T4                                // + lane = byte offset in the dictionary
@@ -2418,7 +2483,11 @@
     v_lshlrev_b32 VT1, 3, VT1
     s_bfm_b64 exec, T3, T4
     v_lshrrev_b64 v[54:55], VT1, s[14:15]
+#ifdef BRX_WIN_SGPR
     v_mov_b32 VPEND, v54                                // suffix bytes
+#else
+    v_and_b32 VPEND, 0xff, v54                          // suffix bytes
+#endif
     s_mov_b64 exec, XLOOP
     s_add_u32 PFREE, PFREE, CLEN
     s_add_u32 POS, POS, CLEN

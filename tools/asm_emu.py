@@ -66,7 +66,7 @@ def disassemble(src):
     return prog
 
 
-_MODS = re.compile(r"\s+(offset:\d+|offen|off|glc|slc|sc0|sc1|nt|lds|gds|row_shr:\d+|row_mask:0x[0-9a-f]+|bank_mask:0x[0-9a-f]+|bound_ctrl:\d+)\b")
+_MODS = re.compile(r"\s+(offset:\d+|offen|off|glc|slc|sc0|sc1|nt|lds|gds|row_shr:\d+|wave_shr:\d+|row_mask:0x[0-9a-f]+|bank_mask:0x[0-9a-f]+|bound_ctrl:\d+)\b")
 
 
 def parse_operand(tok):
@@ -129,7 +129,7 @@ def decode_program(prog):
             for m in _MODS.findall(" " + args):
                 if m.startswith("offset:"):
                     i.mods["offset"] = int(m[7:])
-                elif m.startswith(("row_shr:", "row_mask:", "bank_mask:", "bound_ctrl:")):
+                elif m.startswith(("row_shr:", "wave_shr:", "row_mask:", "bank_mask:", "bound_ctrl:")):
                     k_, v_ = m.split(":")
                     i.mods[k_] = int(v_, 0)
                 else:
@@ -330,7 +330,7 @@ class Wave:
                 if r in self.pend:
                     if loadish and k < (ops[0][2] if ops else 0):
                         continue  # another load into a register with a load in flight (other lanes / in-order counter)
-                    if op == "v_mov_b32" and k == 0 and r[0] == "v":
+                    if op in ("v_mov_b32", "v_and_b32") and k == 0 and r[0] == "v":
                         # a VALU write to lanes that no load in flight will write (prefix / suffix bytes of a transformed word joining
                         # the pending lanes): the register file is written per lane
                         mine = self.exec_mask()
@@ -619,6 +619,17 @@ class Wave:
             for l in range(64):
                 if (m_ is None or m_[l]) and (l & 15) >= n_ and (m_ is None or m_[l - n_]):
                     old_[l] = src_[l - n_]
+            self.V[ops[0][1]] = old_
+        elif op == "v_or_b32_dpp":
+            # wave_shr:1 (LAND_BODY_CTX): lane l takes src0 of lane l - 1 of the WAVE, across the rows of 16; a lane whose source is
+            # out of range or switched off is not written (bound_ctrl off); src1 is the lane's own; all rows and banks enabled
+            if i.mods.get("row_mask", 15) != 15 or i.mods.get("bank_mask", 15) != 15 or i.mods.get("bound_ctrl") or i.mods.get("wave_shr") != 1:
+                raise EmuError("dpp form? " + i.text)
+            a_, b_, old_ = self.vsrc(ops[1]).copy(), self.vsrc(ops[2]).copy(), self.V[ops[0][1]].copy()
+            m_ = self.exec_mask()
+            for l in range(1, 64):
+                if m_ is None or (m_[l] and m_[l - 1]):
+                    old_[l] = a_[l - 1] | b_[l]
             self.V[ops[0][1]] = old_
         elif op == "v_readlane_b32":
             self.cycles += LAT["cross"]
