@@ -26,6 +26,7 @@ REF_PANIC = 26
 
 DIGEST_KINDS = {"crc32": 1, "crc32c": 2}  # BRX_DIGEST_*
 INDEX_NO_QUOTE = 1  # BRX_INDEX_NO_QUOTE
+INDEX_NO_ESCAPE = 2  # BRX_INDEX_NO_ESCAPE (brx_index_set_batch only)
 
 
 class BrxError(RuntimeError):
@@ -90,6 +91,10 @@ def load_library():
     L.brx_index_escaped_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    L.brx_index_set_batch.restype = ctypes.c_int
+    L.brx_index_set_batch.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
     L.brx_find_batch.restype = ctypes.c_int
     L.brx_find_batch.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
@@ -150,7 +155,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
-                    "brx_find_batch", "brx_index_escaped_batch"]
+                    "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch"]
 
 
 def status_str(code: int) -> str:
@@ -421,6 +426,47 @@ class Context:
             pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
         self.index_escaped_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
         return count, open_, pos_off, pos[:total]
+
+    def index_set_batch_device(self, delims, quote, escape, flags, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, open_ptr=None,
+                               pos_off_ptr=None, pos_ptr=None, what_ptr=None, total=0, hip_stream=None):
+        """brx_index_set_batch on raw device pointers: index_escaped_batch_device with a set of delimiters (`delims`: bytes, 1 .. 8
+        distinct values, host memory, taken during the call) and with flags = INDEX_NO_QUOTE | INDEX_NO_ESCAPE switching the quote and
+        the escape off; with pos_off / pos also what[pos_off[i] + k] (uint8, may be None) = the byte at the k-th boundary of stream i."""
+        delims = bytes(delims)
+        rc = self._lib.brx_index_set_batch(self._h, delims, len(delims), quote, escape, flags, out_ptr, out_off_ptr, len_ptr, n, span,
+                                           count_ptr, open_ptr, pos_off_ptr, pos_ptr, what_ptr, total, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_index_set_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def index_set_batch(self, out, out_off, out_len, delims=b",\n", quote=0x22, escape=0x5C, no_quote=False, no_escape=False, stream=None,
+                        positions=True):
+        """Boundaries of the decoded streams of a batch at a SET of delimiter bytes (`delims`: bytes, 1 .. 8 distinct values -- b",\\n"
+        for CSV fields and records, b"{}[]:,\\n" for the structure of JSON Lines), on the device, under the rule of index_escaped_batch:
+        a byte of the set counts where it is not escaped and outside quotes.  no_quote: no byte is a quote; no_escape: no byte is an
+        escape (alone: RFC 4180; both: a plain index of the set).  Arguments otherwise as for index_batch.  Returns (count, open,
+        pos_off, pos, what) -- what index_escaped_batch returns and `what`, a uint8 device tensor with the byte that stands at each
+        position -- or (count, open) with positions=False.  With positions the call reads the grand total back to allocate `pos`
+        and `what`, as index_batch does."""
+        import torch
+        n = int(out_len.numel())
+        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass writes every entry)
+        open_ = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)[:n]
+        hs = stream.cuda_stream if stream is not None else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        flags = (INDEX_NO_QUOTE if no_quote else 0) | (INDEX_NO_ESCAPE if no_escape else 0)
+        args = (bytes(delims), int(quote), int(escape), flags, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
+        self.index_set_batch_device(*args, count.data_ptr(), open_.data_ptr(), hip_stream=hs)
+        if not positions:
+            return count, open_
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ends = torch.cumsum(count, 0)
+            pos_off = ends - count
+            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
+            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
+            what = torch.empty(max(total, 1), dtype=torch.uint8, device=out.device)
+        self.index_set_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), what.data_ptr(), total, hip_stream=hs)
+        return count, open_, pos_off, pos[:total], what[:total]
 
     def find_batch_device(self, needle, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr=None, pos_ptr=None, total=0,
                           hip_stream=None):

@@ -234,6 +234,8 @@ struct brx_ctx {
     PassRing index_quoted_ring;
     // brx_index_escaped_batch (brx_index_escaped.hip): scratch (ticket counters, tile prefix sums, two words per tile)
     PassRing index_escaped_ring;
+    // brx_index_set_batch (brx_index_escaped.hip): scratch as for brx_index_escaped_batch, a ring of its own
+    PassRing index_set_ring;
     // brx_find_batch (brx_find.hip): scratch (ticket counters, tile prefix sums, per-tile counts)
     PassRing find_ring;
     std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
@@ -324,6 +326,7 @@ static void ctx_release(brx_ctx *c) {
     ring_free(c->index_ring);
     ring_free(c->index_quoted_ring);
     ring_free(c->index_escaped_ring);
+    ring_free(c->index_set_ring);
     ring_free(c->find_ring);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -1443,6 +1446,62 @@ extern "C" int brx_index_escaped_batch(brx_ctx *c, uint8_t delim, uint8_t quote,
                                  total, c->max_grid / 4u, st);
         HIP_TRY(hipGetLastError());
         if ((rc = ring_record(c->index_escaped_ring, st)) != BRX_SUCCESS) return rc;
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- boundaries at a set of delimiter bytes, with optional quote and escape, of the decoded streams of a batch (brx_index_escaped.hip)
+extern "C" int brx_index_set_batch(brx_ctx *c, const uint8_t *delims, uint32_t n_delims, uint8_t quote, uint8_t escape, uint32_t flags,
+                                   const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                                   uint64_t *count, uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint8_t *what,
+                                   uint64_t total, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: ctx is NULL");
+    if (flags & ~(BRX_INDEX_NO_QUOTE | BRX_INDEX_NO_ESCAPE)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: unknown flag bits");
+    if (!delims) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: delims is NULL");
+    if (n_delims == 0 || n_delims > BRX_INDEX_SET_MAX)
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: n_delims must be 1 .. 8 (delims)");
+    // the set as the kernels take it: byte k of one 64-bit launch argument (read here: the caller may reuse `delims` at once)
+    uint64_t set = 0;
+    for (uint32_t k = 0; k < n_delims; k++) {
+        for (uint32_t j = 0; j < k; j++)
+            if (delims[j] == delims[k]) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: a byte stands twice in delims");
+        set |= (uint64_t)delims[k] << (8u * k);
+    }
+    static_assert(BRX_INDEX_SET_NO_QUOTE == BRX_INDEX_NO_QUOTE && BRX_INDEX_SET_NO_ESCAPE == BRX_INDEX_NO_ESCAPE, "the kernels' flags are brx.h's");
+    const bool quotes = !(flags & BRX_INDEX_NO_QUOTE), escapes = !(flags & BRX_INDEX_NO_ESCAPE);
+    for (uint32_t k = 0; escapes && k < n_delims; k++)
+        if (delims[k] == escape) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: escape is one of delims");
+    for (uint32_t k = 0; quotes && k < n_delims; k++)
+        if (delims[k] == quote) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: quote is one of delims");
+    if (quotes && escapes && quote == escape)
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: quote and escape are the same byte");
+    if ((pos_off == nullptr) != (pos == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: pos_off and pos go together");
+    if (what && !pos) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: what is given without pos");
+    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: count is NULL in count mode");
+    if (n == 0) return BRX_SUCCESS;
+    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: NULL table");
+    // what the scratch of a launch must hold follows from n and span alone: no length is read back
+    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
+    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: span out of range");
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        int rc = ring_reserve(c->index_set_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
+                              brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                              "set index scratch allocation failed");
+        void *scratch = nullptr;
+        if (rc == BRX_SUCCESS) rc = ring_take(c->index_set_ring, &scratch);
+        if (rc != BRX_SUCCESS) return rc;
+        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+        brx_launch_index_set(out, out_off, len, n, span, set, n_delims, quote, escape, flags, scratch, max_tiles, count, open, pos_off,
+                             pos, what, total, c->max_grid / 4u, st);
+        HIP_TRY(hipGetLastError());
+        if ((rc = ring_record(c->index_set_ring, st)) != BRX_SUCCESS) return rc;
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;

@@ -102,3 +102,12 @@ void brx_launch_index_escaped(const void *out, const uint64_t *out_off, const ui
                               uint8_t quote, uint8_t escape, uint32_t flags, void *scratch, uint64_t max_tiles, uint64_t *count,
                               uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint64_t total, unsigned workgroups,
                               void *hip_stream);
+
+// brx_index_set_batch: the same scratch region, tile word, state maps and resolve kernel, with a set of 1 .. 8 delimiter bytes (byte k
+// of `set` for k < n_delims) and with the escape switched off by a flag as the quote is
+#define BRX_INDEX_SET_NO_QUOTE 1u  // == BRX_INDEX_NO_QUOTE of brx.h
+#define BRX_INDEX_SET_NO_ESCAPE 2u // == BRX_INDEX_NO_ESCAPE of brx.h
+void brx_launch_index_set(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint64_t set,
+                          uint32_t n_delims, uint8_t quote, uint8_t escape, uint32_t flags, void *scratch, uint64_t max_tiles,
+                          uint64_t *count, uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint8_t *what, uint64_t total,
+                          unsigned workgroups, void *hip_stream);

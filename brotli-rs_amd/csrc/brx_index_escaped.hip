@@ -276,3 +276,176 @@ void brx_launch_index_escaped(const void *out, const uint64_t *out_off, const ui
                        span, (uint32_t)delim, (uint32_t)quote, (uint32_t)escape, quotes, pre, max_tiles, words, pos_off, pos, total,
                        brx_tp_ticket_b(scratch));
 }
+
+// ---- brx_index_set_batch: the same pass with a set of 1 .. 8 delimiter bytes, and with the escape as optional as the quote --------
+// A delimiter never changes the carried state, so "is the delimiter" becomes "is one of the set" in the row body and nothing else
+// moves: ie_row, ie_exit_escape, the tile word, the resolve kernel above and ie_select / ie_tile_map are the escaped pass's own.  The
+// set travels as launch arguments (byte k of `set` for k < nd: SGPRs), the loop over it is wave-uniform.
+
+// bit k: byte k of the chunk is one of the nd (1 .. 8) bytes of `set`: the OR of ie_mask over the set, taken before the bits are
+// gathered so that the gathering is done once
+__device__ __forceinline__ uint32_t is_mask(uint4 v, uint64_t set, uint32_t nd) {
+    uint32_t x = 0, y = 0, z = 0, w = 0;
+    for (uint32_t k = 0; k < nd; k++) { // (uniform)
+        const uint32_t d4 = ((uint32_t)set & 0xFFu) * 0x01010101u;
+        set >>= 8;
+        x |= ix_eq(v.x, d4);
+        y |= ix_eq(v.y, d4);
+        z |= ix_eq(v.z, d4);
+        w |= ix_eq(v.w, d4);
+    }
+    return ix_nib(x) | (ix_nib(y) << 4) | (ix_nib(z) << 8) | (ix_nib(w) << 12);
+}
+
+// ie_filler for the set: a byte that is no delimiter, not the quote if there is one and not the escape if there is one, four times.
+// At most 10 values are excluded, so the walk ends at 10 or before.
+__device__ __forceinline__ uint32_t is_filler(uint64_t set, uint32_t nd, uint32_t quote, uint32_t quotes, uint32_t escape,
+                                              uint32_t escapes) {
+    uint32_t f = 0u;
+    for (;;) {
+        bool hit = (quotes && f == quote) || (escapes && f == escape);
+        for (uint32_t k = 0; k < nd; k++) hit = hit || f == ((uint32_t)(set >> (8u * k)) & 0xFFu);
+        if (!hit) break;
+        f++;
+    }
+    return f * 0x01010101u;
+}
+
+// byte k of the chunk
+__device__ __forceinline__ uint32_t is_byte(uint4 v, uint32_t k) {
+    const uint32_t w = k & 8u ? (k & 4u ? v.w : v.z) : (k & 4u ? v.y : v.x);
+    return w >> (8u * (k & 3u)) & 0xFFu;
+}
+
+// brx_index_escaped_count_kernel with the union mask; `escapes` = 0 forces the escape mask to 0 as `quotes` = 0 does the quote mask.
+// The tile word is the escaped pass's, BRX_IE_LEAD_DELIM meaning "a byte of the set".
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_set_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                                                           const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
+                                                                           uint64_t set, uint32_t nd, uint32_t quote, uint32_t escape,
+                                                                           uint32_t quotes, uint32_t escapes,
+                                                                           const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                                                           uint64_t *__restrict__ tile_word, unsigned long long *ticket) {
+    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles; // (more tiles than `span` allows: a caller's error, nothing is written for them)
+    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
+    const uint32_t q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
+    const uint32_t qon = quotes ? 0xFFFFu : 0u, eon = escapes ? 0xFFFFu : 0u;
+    const uint32_t f4 = is_filler(set, nd, quote, quotes, escape, escapes);
+    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
+    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
+    while (item < total) {
+        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+        uint32_t all = 0, odd = 0, rp = 0, re = 0, em = 0, esc = 0;
+        uint32_t lead = 4u, rodd = 0; // 4: the leading run of escape bytes has not ended yet
+        uint64_t row = it.t0;
+        for (uint32_t r = 0; r < it.rows; r++) {
+            row = it.t0 + (uint64_t)r * BRX_TP_ROW;
+            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
+            em = ie_mask(v, e4) & eon;
+            const uint32_t qm = ie_mask(v, q4) & qon, dm = is_mask(v, set, nd);
+            uint32_t in;
+            uint64_t some;
+            esc = ie_row(em, qm, lane, re, rp, in, some);
+            if (lead == 4u && some) { // (uniform) once per tile: the first byte that is no escape byte
+                const uint32_t fl = (uint32_t)__ffsll((long long)some) - 1u;
+                const uint32_t k = (uint32_t)__ffs((int)(~em & 0xFFFFu)) - 1u; // (a lane without one: not the lane that is read)
+                const uint32_t mine = (k & 15u) | ((dm >> (k & 15u) & 1u) << 4) | ((qm >> (k & 15u) & 1u) << 5);
+                const uint32_t got = (uint32_t)__shfl((int)mine, (int)fl);
+                rodd = got & 1u;
+                lead = row + 16u * fl + (got & 15u) >= it.e ? BRX_IE_LEAD_ALL : got >> 4; // (filler behind the stream's end is no byte of it)
+            }
+            const uint32_t m = dm & ~esc;
+            all += __popc(m);
+            odd += __popc(m & in);
+        }
+        if (lead == 4u) lead = BRX_IE_LEAD_ALL;
+        const uint32_t x = ie_exit_escape(em, esc, lane, row, it.t1);
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) {
+            all += (uint32_t)__shfl_xor((int)all, k);
+            odd += (uint32_t)__shfl_xor((int)odd, k);
+        }
+        if (lane == 0u)
+            tile_word[item] = (uint64_t)(all - odd) | ((uint64_t)odd << BRX_IE_C0_BITS) | ((uint64_t)rp << BRX_IE_PAR_SHIFT) |
+                              ((uint64_t)x << BRX_IE_X_SHIFT) | ((uint64_t)lead << BRX_IE_LEAD_SHIFT) |
+                              ((uint64_t)rodd << BRX_IE_RODD_SHIFT);
+        item = tp_next(ticket, grid_waves, total, lane);
+    }
+}
+
+// brx_index_escaped_fill_kernel with the union mask; next to every position goes the byte that stands there, taken from the chunk in
+// registers (`what` may be NULL)
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_set_fill_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                                                          const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
+                                                                          uint64_t set, uint32_t nd, uint32_t quote, uint32_t escape,
+                                                                          uint32_t quotes, uint32_t escapes,
+                                                                          const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                                                          const uint64_t *__restrict__ tile_word,
+                                                                          const uint64_t *__restrict__ pos_off, uint64_t *__restrict__ pos,
+                                                                          uint8_t *__restrict__ what, uint64_t pos_total,
+                                                                          unsigned long long *ticket) {
+    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
+    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
+    const uint32_t q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
+    const uint32_t qon = quotes ? 0xFFFFu : 0u, eon = escapes ? 0xFFFFu : 0u;
+    const uint32_t f4 = is_filler(set, nd, quote, quotes, escape, escapes);
+    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
+    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
+    while (item < total) {
+        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+        const uint64_t w = tp_uniform(tile_word[item]);
+        // index in pos of the tile's first boundary: the stream's first entry + those of the stream's tiles in front of this one
+        uint64_t base = tp_uniform(pos_off[it.si] + ((w & BRX_IE_G_MASK) - (tile_word[pre[it.si]] & BRX_IE_G_MASK)));
+        uint32_t rp = (uint32_t)(w >> BRX_IE_ENTRY_SHIFT) & 1u, re = (uint32_t)(w >> (BRX_IE_ENTRY_SHIFT + 1u)) & 1u;
+        for (uint32_t r = 0; r < it.rows; r++) {
+            const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
+            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
+            uint32_t in;
+            uint64_t some;
+            const uint32_t esc = ie_row(ie_mask(v, e4) & eon, ie_mask(v, q4) & qon, lane, re, rp, in, some); // (every row: it moves the state on)
+            uint32_t m = is_mask(v, set, nd) & ~esc & ~in; // bit k: byte k of the chunk is a boundary of the stream
+            if (__ballot(m != 0u) == 0ull) continue; // (uniform) a row without one: no position work
+            const uint32_t c = (uint32_t)__popc(m);
+            uint32_t incl = c;
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, s);
+                if (lane >= (uint32_t)s) incl += up;
+            }
+            uint64_t idx = base + (incl - c);
+            const uint64_t rel = row + 16u * lane - it.a; // offset of the chunk's byte 0 in the stream (m == 0 where that is in front of it)
+            while (m) {
+                const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
+                m &= m - 1u;
+                if (idx < pos_total) {
+                    pos[idx] = rel + k;
+                    if (what) what[idx] = (uint8_t)is_byte(v, k); // (uniform)
+                }
+                idx++;
+            }
+            base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+        item = tp_next(ticket, grid_waves, total, lane);
+    }
+}
+
+void brx_launch_index_set(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint64_t set,
+                          uint32_t n_delims, uint8_t quote, uint8_t escape, uint32_t flags, void *scratch, uint64_t max_tiles,
+                          uint64_t *count, uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint8_t *what, uint64_t total,
+                          unsigned workgroups, void *hip_stream) {
+    uint64_t *pre = brx_tp_pre(scratch), *words = (uint64_t *)brx_tp_own(scratch, n), *exits = words + max_tiles + 1u;
+    const uint32_t quotes = (flags & BRX_INDEX_SET_NO_QUOTE) ? 0u : 1u, escapes = (flags & BRX_INDEX_SET_NO_ESCAPE) ? 0u : 1u;
+    hipStream_t st = (hipStream_t)hip_stream;
+    brx_launch_tile_plan(out, out_off, len, n, scratch, nullptr, 0u, st); // (resolve writes every count[i] and open[i]: nothing to clear)
+    hipLaunchKernelGGL(brx_index_set_count_kernel, dim3(workgroups), dim3(BRX_TP_WG), 0, st, (const uint8_t *)out, out_off, len, n, span,
+                       set, n_delims, (uint32_t)quote, (uint32_t)escape, quotes, escapes, pre, max_tiles, words,
+                       brx_tp_ticket_a(scratch));
+    hipLaunchKernelGGL(brx_index_escaped_resolve_kernel, dim3(1), dim3(1024), 0, st, n, pre, max_tiles, words, exits, count, open);
+    if (!pos) return;
+    hipLaunchKernelGGL(brx_index_set_fill_kernel, dim3(workgroups), dim3(BRX_TP_WG), 0, st, (const uint8_t *)out, out_off, len, n, span,
+                       set, n_delims, (uint32_t)quote, (uint32_t)escape, quotes, escapes, pre, max_tiles, words, pos_off, pos, what,
+                       total, brx_tp_ticket_b(scratch));
+}

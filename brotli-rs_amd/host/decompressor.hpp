@@ -198,6 +198,17 @@ inline void index_escaped_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote, uint
         BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_index_escaped_batch: ") + brx_last_error());
 }
+// The same with a SET of delimiter bytes (`delims`, HOST memory, 1 .. 8 distinct bytes, e.g. ",\n" or "{}[]:,\n") and with the escape
+// as optional as the quote (flags: BRX_INDEX_NO_QUOTE, BRX_INDEX_NO_ESCAPE): a byte of the set is a boundary where it is not escaped
+// and outside quotes; what[pos_off[i] + k] (may be nullptr, only with `pos`) = the byte that stands at pos[pos_off[i] + k].
+inline void index_set_batch(brx_ctx *ctx, const uint8_t *delims, uint32_t n_delims, uint8_t quote, uint8_t escape, uint32_t flags,
+                            const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count,
+                            uint32_t *open = nullptr, const uint64_t *pos_off = nullptr, uint64_t *pos = nullptr, uint8_t *what = nullptr,
+                            uint64_t total = 0, void *stream = nullptr) {
+    if (brx_index_set_batch(ctx, delims, n_delims, quote, escape, flags, out, out_off, len, n, span, count, open, pos_off, pos, what,
+                            total, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_index_set_batch: ") + brx_last_error());
+}
 // Occurrences of a byte sequence (`needle`, HOST memory, 1 .. 16 bytes, e.g. "\r\n") in the same batch: count[i] = occurrences in
 // stream i, overlapping ones included; with `pos_off` and `pos` also the offset within the stream of each one's first byte, ascending.
 inline void find_batch(brx_ctx *ctx, const uint8_t *needle, uint32_t needle_len, const uint8_t *out, const uint64_t *out_off,

@@ -382,7 +382,8 @@ int brx_index_quoted_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote,
  *             dialects above.  Other bits must be 0.
  * With delim = ',' the same call gives the field separators; for JSON Lines those are the commas outside strings.
  * Not in scope: delimiters, quotes or escapes of more than one byte; escapes that act only inside quotes; decoding what an escape
- * sequence means (\n, \uXXXX); CR handling; several delimiters in one call.
+ * sequence means (\n, \uXXXX); CR handling.  Several delimiters in one call (',' and '\n', the structural characters of JSON) and
+ * an RFC 4180 dialect without an escape are brx_index_set_batch below.
  * Everything else is as for brx_index_quoted_batch: device pointers only; out, out_off, len, n and span as there (nothing at or beyond
  * out + span, or in front of out, is ever loaded); count mode (pos_off == NULL and pos == NULL; count required) and fill mode (pos_off
  * and pos both given; count may be NULL, and if given it is written as in count mode; `total` bounds the entries written to pos);
@@ -404,6 +405,54 @@ int brx_index_escaped_batch(brx_ctx *ctx, uint8_t delim, uint8_t quote, uint8_t 
                             uint64_t *count, uint32_t *open,
                             const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                             void *hip_stream);
+
+/* ---- boundaries at a set of delimiter bytes, with optional quote and escape (device memory only) ---------
+ * Hardly any consumer of delimited text wants one kind of boundary: a CSV reader needs the field separators and the record ends (','
+ * '\n', often '\r'), a JSON Lines parser the structural characters outside strings ('{' '}' '[' ']' ':' ',' and the line feed),
+ * universal newlines are '\r' or '\n'.  With the passes above that is one fill-mode call per byte value, each walking the bytes twice,
+ * and a merge of sorted position lists.  This pass takes a SET of 1 .. 8 delimiter bytes, delims[0 .. n_delims), in one call and says
+ * for every position which of them stands there.
+ * Stream i is s = out[out_off[i] .. out_off[i] + len[i]).  esc(j), ACTIVE QUOTES, q(j) and open[i] are word for word those of
+ * brx_index_escaped_batch.
+ *   s[j] is a BOUNDARY iff s[j] is one of delims[0 .. n_delims), byte j is not escaped, and q(j) is even
+ *   count[i]              = number of boundaries of stream i                                                     for i < n
+ *   pos[pos_off[i] + k]   = offset WITHIN stream i of its k-th boundary, ascending in k                           (fill mode)
+ *   what[pos_off[i] + k]  = the byte found there, s[pos[pos_off[i] + k]]: the delimiter's VALUE, not its index in delims  (fill mode)
+ *   open[i]               = two bits, as for brx_index_escaped_batch
+ * Every stream starts unescaped and outside quotes, and nothing behind a stream takes part, as there.
+ *   delims    HOST memory, whatever the other pointers are: n_delims bytes, 1 <= n_delims <= BRX_INDEX_SET_MAX = 8, no value twice,
+ *             read before the call returns.  They travel to the kernels as launch arguments (one 64-bit word and a count) -- no
+ *             upload, no table, no synchronisation -- so the call stays enqueue-only on a caller's stream.
+ *   flags     BRX_INDEX_NO_QUOTE: no byte is a quote -- the `quote` argument is ignored and bit 0 of open[i] is 0.
+ *             BRX_INDEX_NO_ESCAPE: no byte is an escape -- the `escape` argument is ignored and bit 1 of open[i] is 0.  Alone it is
+ *             the rule of RFC 4180 (brx_index_quoted_batch with a set); both flags give a plain index of the byte set.  Other bits
+ *             must be 0.  (brx_index_escaped_batch does not take BRX_INDEX_NO_ESCAPE.)
+ *   what      DEVICE memory, `total` entries of one byte, bounded by `total` as pos is.  May be NULL; allowed only together with pos.
+ * Check values: s = {"a":"x,\"y:}","b":[1,2]}\n{"c":"\\"}\n{"open":"[\  (48 bytes), delims "{}[]:,\n", quote '"', escape '\', flags 0:
+ * pos 0 4 14 18 19 21 23 24 25 26 30 35 36 37 44, what {:,:[,]}\n{:}\n{: and open 3.  s = a,"b,c\n",d\r\ne,"f""g",h\n"x (25 bytes),
+ * delims ",\n\r", quote '"': with BRX_INDEX_NO_ESCAPE pos 1 8 10 11 13 20 22 and open 1; with both flags pos 1 4 6 8 10 11 13 20 22
+ * and open 0.
+ * Not in scope: more than 8 delimiters; byte ranges or classes; delimiters, quotes or escapes of more than one byte (brx_find_batch
+ * finds a sequence); escapes that act only inside quotes; decoding what an escape sequence means; and the three index entry points
+ * above are not re-expressed over this pass's kernels: their code paths stay as they shipped.
+ * Everything else is as for brx_index_escaped_batch: all other pointers are device memory; out, out_off, len, n and span as there
+ * (nothing at or beyond out + span, or in front of out, is ever loaded); count mode (pos_off == NULL and pos == NULL; count required)
+ * and fill mode (pos_off and pos both given; count may be NULL; `total` bounds the entries written to pos and what); `open` may be
+ * NULL in either mode; hip_stream as there.  Scratch is sized as there and is a ring of 16 regions of this pass's own.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits; delims NULL; n_delims 0
+ * or above 8; a value twice in delims; without BRX_INDEX_NO_ESCAPE a delimiter equal to escape; without BRX_INDEX_NO_QUOTE quote equal
+ * to a delimiter; with neither flag quote == escape; only one of pos_off / pos; what without pos; count NULL in count mode; then
+ * n = 0 returns BRX_SUCCESS, no launch; then out_off or len NULL, span out of range.
+ * Count mode is one pass over the bytes and a one-workgroup pass over the tiles, fill mode a second pass over the bytes plus 9 bytes
+ * per boundary; no reference counterpart. */
+#define BRX_INDEX_NO_ESCAPE 2u /* brx_index_set_batch only */
+#define BRX_INDEX_SET_MAX 8u
+int brx_index_set_batch(brx_ctx *ctx, const uint8_t *delims, uint32_t n_delims, uint8_t quote, uint8_t escape, uint32_t flags,
+                        const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
+                        uint64_t span,
+                        uint64_t *count, uint32_t *open,
+                        const uint64_t *pos_off, uint64_t *pos, uint8_t *what, uint64_t total,
+                        void *hip_stream);
 
 /* ---- occurrences of a byte sequence in the decoded bytes of a batch (device memory only) -----------------
  * Much delimited text does not end its records with one byte: CRLF text ("\r\n", a lone "\n" is data), blank-line separated records

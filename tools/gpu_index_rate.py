@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times brx_index_batch, brx_index_quoted_batch, brx_index_escaped_batch (record boundaries of a decoded batch, on the device; the
-second with RFC 4180 quoting, quote = '"'; the third with an escape byte on top, escape = '\\') and brx_find_batch with HIP events,
-in one run:
+second with RFC 4180 quoting, quote = '"'; the third with an escape byte on top, escape = '\\'), brx_index_set_batch (the third with a
+set of delimiters and optional quote and escape) and brx_find_batch with HIP events, in one run:
 
   headline  the decoded output of N x alice29 (default 4096) in device memory, delim = '\\n': count mode and fill mode of the three calls
             (pos_off from a count-mode call and torch.cumsum, outside the timed window), brx_compact_batch over the same slots (the
@@ -14,6 +14,11 @@ Behind the six modes of each batch (the escaped ones with their ratio to the quo
 16 bytes that occur in the data -- for alice29 its line feed, its line ending CR LF, "the " and "the Mock Turtle "; for the random
 bytes a line feed, two line feeds, and 4 and 16 bytes taken from the data -- in count mode and fill mode, each with its ratio to the
 brx_index_batch line of the same batch and mode.
+
+Behind them come the set lines: brx_index_set_batch in count mode and fill mode (with `what`) for b"\\n", b",\\n" and b"{}[]:,\\n" at
+flags 0, b",\\n" under BRX_INDEX_NO_ESCAPE and b"\\r\\n" under both flags, each with its ratio to the brx_index_escaped_batch line of the same
+batch and mode; the one-delimiter line says whether it lies within the spread (min .. max) of the escaped pass's repetitions, and the
+b",\\n" fill line carries its ratio to the two brx_index_escaped_batch fill calls (one for '\\n', one for ',') that it replaces.
 
 Every timed call is warmed up first, timed `--reps` times in windows of `--inner` back-to-back calls between two events; the median
 and the spread of the per-call times are printed.  Counts and positions are checked against numpy on the host (not in the timed
@@ -31,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from brotli_rs_amd import brx  # noqa: E402
 import brx_knobs  # noqa: E402
 import escaped_oracle  # noqa: E402
+import set_oracle  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=4096)
@@ -80,7 +86,7 @@ def quoted_reference(s):
 
 def index_rates(name, arena, offs, lens, stream_bytes):
     """Count mode and fill mode of brx_index_batch, brx_index_quoted_batch and brx_index_escaped_batch over one batch; stream_bytes(i) -> the bytes of
-    stream i as a numpy array (results checked on a sample).  -> {mode: median ms}"""
+    stream i as a numpy array (results checked on a sample).  -> {mode: median ms}, {mode: (median, min, max) ms}"""
     n = lens.numel()
     total_bytes = int(lens.sum().item())
     base = (arena.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, arena.numel())
@@ -127,7 +133,66 @@ def index_rates(name, arena, offs, lens, stream_bytes):
     for mode in ("count", "fill"):
         say("%-9s escaped %-5s = %.3f x quoted %s, %.3f x index %s" % (name, mode, res["escaped " + mode][0] / res["quoted " + mode][0], mode,
                                                                       res["escaped " + mode][0] / res["index " + mode][0], mode))
-    return {m: v[0] for m, v in res.items()}
+    return {m: v[0] for m, v in res.items()}, res
+
+
+SET_CASES = ((b"\n", 0), (b",\n", 0), (b"{}[]:,\n", 0), (b",\n", brx.INDEX_NO_ESCAPE), (b"\r\n", brx.INDEX_NO_QUOTE | brx.INDEX_NO_ESCAPE))
+
+
+def set_rates(name, arena, offs, lens, stream_bytes, escaped):
+    """Count mode and fill mode (with `what`) of brx_index_set_batch over one batch for every case of SET_CASES (results checked on a
+    sample); escaped = the (median, min, max) of index_rates for the same batch: the yardstick of every line.  The two escaped fill
+    calls that the b",\\n" case replaces: the '\\n' one of index_rates and a ',' one timed here."""
+    n = lens.numel()
+    total_bytes = int(lens.sum().item())
+    base = (arena.data_ptr(), offs.data_ptr(), lens.data_ptr(), n, arena.numel())
+    sample = sorted(set(np.linspace(0, n - 1, 16).astype(int).tolist()))
+    count = torch.zeros(n, dtype=torch.int64, device=dev)
+    open_ = torch.zeros(n, dtype=torch.int32, device=dev)
+    ctx.index_escaped_batch_device(0x2C, QUOTE, ESCAPE, 0, *base, count.data_ptr(), open_.data_ptr(), hip_stream=stream.cuda_stream)
+    stream.synchronize()
+    comma_off = torch.cumsum(count, 0) - count
+    comma_entries = int(count.sum().item())
+    comma_pos = torch.zeros(max(comma_entries, 1), dtype=torch.int64, device=dev)
+    comma_ms, lo, hi = timed(lambda: ctx.index_escaped_batch_device(0x2C, QUOTE, ESCAPE, 0, *base, None, None, comma_off.data_ptr(),
+                                                                    comma_pos.data_ptr(), comma_entries, hip_stream=stream.cuda_stream))
+    say("%-9s escaped fill ','  %9.3f ms  (min %.3f, max %.3f)   [%d entries]" % (name, comma_ms, lo, hi, comma_entries))
+    for delims, flags in SET_CASES:
+        tag = "set %s%s" % ("".join("%02x" % b for b in delims), {0: "", 1: " nq", 2: " ne", 3: " nq ne"}[flags])
+
+        def call(count_ptr, open_ptr, *fill):
+            ctx.index_set_batch_device(delims, QUOTE, ESCAPE, flags, *base, count_ptr, open_ptr, *fill, hip_stream=stream.cuda_stream)
+
+        def count_call():
+            call(count.data_ptr(), open_.data_ptr())
+        count_call()
+        stream.synchronize()
+        res = {"count": timed(count_call)}
+        pos_off = torch.cumsum(count, 0) - count
+        entries = int(count.sum().item())
+        pos = torch.zeros(max(entries, 1), dtype=torch.int64, device=dev)
+        what = torch.zeros(max(entries, 1), dtype=torch.uint8, device=dev)
+
+        def fill_call():
+            call(None, None, pos_off.data_ptr(), pos.data_ptr(), what.data_ptr(), entries)
+        res["fill"] = timed(fill_call)
+        h_count, h_open, h_off, h_pos, h_what = count.cpu().numpy(), open_.cpu().numpy(), pos_off.cpu().numpy(), pos.cpu().numpy(), what.cpu().numpy()
+        for i in sample:
+            want, want_what, want_open = set_oracle.vec(stream_bytes(i), delims, QUOTE, ESCAPE, bool(flags & brx.INDEX_NO_QUOTE),
+                                                        bool(flags & brx.INDEX_NO_ESCAPE))
+            assert h_count[i] == want.size, "%s %s: count of stream %d differs from numpy" % (name, tag, i)
+            assert h_open[i] == want_open, "%s %s: open of stream %d differs from numpy" % (name, tag, i)
+            assert (h_pos[h_off[i]:h_off[i] + h_count[i]] == want).all(), "%s %s: positions of stream %d differ from numpy" % (name, tag, i)
+            assert (h_what[h_off[i]:h_off[i] + h_count[i]] == want_what).all(), "%s %s: what of stream %d differs from numpy" % (name, tag, i)
+        for mode, (med, lo, hi) in res.items():
+            e_med, e_lo, e_hi = escaped["escaped " + mode]
+            more = ""
+            if delims == b"\n" and flags == 0:
+                more = "  (escaped %.3f .. %.3f: %s its spread)" % (e_lo, e_hi, "within" if e_lo <= med <= e_hi else "OUTSIDE")
+            if delims == b",\n" and flags == 0 and mode == "fill":
+                more = "  = %.3f x two escaped fills (%.3f ms)" % (med / (e_med + comma_ms), e_med + comma_ms)
+            say("%-9s %-24s %-5s  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s  = %.3f x escaped %-5s  [%d entries]%s"
+                % (name, tag, mode, med, lo, hi, total_bytes / med / 1e6, med / e_med, mode, entries, more))
 
 
 def find_reference(s, needle):
@@ -214,10 +279,11 @@ def digest_call():
 digest_ms, lo, hi = timed(digest_call)
 say("headline  digest crc32  %9.3f ms  (min %.3f, max %.3f)  %7.1f GB/s" % (digest_ms, lo, hi, n * len(text) / digest_ms / 1e6))
 np_text = np.frombuffer(text, dtype=np.uint8)
-res = index_rates("headline", out, out_off, out_len, lambda i: np_text)
+res, spreads = index_rates("headline", out, out_off, out_len, lambda i: np_text)
 for mode, ms in res.items():
     say("headline  %-12s = %.3f x compact, %.3f x digest" % (mode, ms / compact_ms, ms / digest_ms))
 find_rates("headline", out, out_off, out_len, lambda i: np_text, (b"\n", b"\r\n", b"the ", b"the Mock Turtle "), res)
+set_rates("headline", out, out_off, out_len, lambda i: np_text, spreads)
 del blob, dst
 
 # ---- one large stream ------------------------------------------------------------------------------------------------
@@ -227,9 +293,10 @@ big_n = (70 << 20) + 12345
 arena = torch.randint(0, 256, (big_n + 64,), dtype=torch.uint8, device=dev, generator=g)
 host = arena.cpu().numpy()
 big_off, big_len = torch.tensor([3], dtype=torch.int64, device=dev), torch.tensor([big_n], dtype=torch.int64, device=dev)
-res = index_rates("large", arena, big_off, big_len, lambda i: host[3:3 + big_n])
+res, spreads = index_rates("large", arena, big_off, big_len, lambda i: host[3:3 + big_n])
 find_rates("large", arena, big_off, big_len, lambda i: host[3:3 + big_n],
            (b"\n", b"\n\n", host[100000:100004].tobytes(), host[200000:200016].tobytes()), res)
+set_rates("large", arena, big_off, big_len, lambda i: host[3:3 + big_n], spreads)
 
 # ---- 4096 log-uniform lengths -------------------------------------------------------------------------------------------
 rng = np.random.default_rng(1234)
@@ -243,10 +310,11 @@ arena = torch.randint(0, 256, (int(h_offs[-1] + slots[-1]),), dtype=torch.uint8,
 host = arena.cpu().numpy()
 d_offs, d_lens = torch.from_numpy(h_offs).to(dev), torch.from_numpy(h_lens).to(dev)
 big = int(np.argmax(h_lens))  # (the 4- and 16-byte needles are bytes of the longest stream)
-res = index_rates("ragged", arena, d_offs, d_lens, lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]])
+res, spreads = index_rates("ragged", arena, d_offs, d_lens, lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]])
 find_rates("ragged", arena, d_offs, d_lens, lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]],
            (b"\n", b"\n\n", host[h_offs[big] + 1000:h_offs[big] + 1004].tobytes(), host[h_offs[big] + 2000:h_offs[big] + 2016].tobytes()),
            res)
+set_rates("ragged", arena, d_offs, d_lens, lambda i: host[h_offs[i]:h_offs[i] + h_lens[i]], spreads)
 ctx.close()
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
