@@ -27,6 +27,8 @@ REF_PANIC = 26
 DIGEST_KINDS = {"crc32": 1, "crc32c": 2}  # BRX_DIGEST_*
 INDEX_NO_QUOTE = 1  # BRX_INDEX_NO_QUOTE
 INDEX_NO_ESCAPE = 2  # BRX_INDEX_NO_ESCAPE (brx_index_set_batch only)
+TAKE_NO_DELIM = 1  # BRX_TAKE_NO_DELIM
+TAKE_TRIM_CR = 2  # BRX_TAKE_TRIM_CR (only with TAKE_NO_DELIM)
 
 
 class BrxError(RuntimeError):
@@ -99,6 +101,11 @@ def load_library():
     L.brx_find_batch.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                  ctypes.c_void_p]
+    L.brx_take_batch.restype = ctypes.c_int
+    L.brx_take_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_uint64, ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -155,7 +162,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
-                    "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch"]
+                    "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch"]
 
 
 def status_str(code: int) -> str:
@@ -502,6 +509,67 @@ class Context:
             pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
         self.find_batch_device(*args, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
         return count, pos_off, pos[:total]
+
+    def take_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
+                          sel_stream_ptr, sel_rec_ptr, m, rec_len_ptr, dst_off_ptr=None, dst_ptr=None, total=0, hip_stream=None):
+        """brx_take_batch on raw device pointers: entry j of the selection is record sel_rec[j] of stream sel_stream[j] (uint32 / uint64;
+        both None: every record of every stream in turn, m = sum(count) + n) under the positions count / pos_off / pos of an index or
+        find pass (delim_len = 1, or the needle's length).  Size mode (dst_off_ptr and dst_ptr None): rec_len[j] = the record's length.
+        Fill mode: dst[dst_off[j] + t] = the record's byte t for t below its length and its room; nothing at or beyond `total` is
+        written.  flags: TAKE_NO_DELIM | TAKE_TRIM_CR."""
+        rc = self._lib.brx_take_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len,
+                                      flags, sel_stream_ptr, sel_rec_ptr, m, rec_len_ptr, dst_off_ptr, dst_ptr, total, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_take_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def take_batch(self, out, out_off, out_len, count, pos_off, pos, sel_stream=None, sel_rec=None, delim_len=1, keep_delim=True,
+                   trim_cr=False, stride=None, stream=None):
+        """The selected records of the decoded streams of a batch, gathered on the device.  out, out_off, out_len and stream as for
+        index_batch; count, pos_off, pos as index_batch, index_quoted_batch, index_escaped_batch, index_set_batch (delim_len = 1) or
+        find_batch (delim_len = len(needle)) returned them.  sel_stream (int32 device tensor) and sel_rec (int64): entry j is record
+        sel_rec[j] of stream sel_stream[j], in any order, repeats allowed, out-of-range entries empty; both None: every record of
+        every stream in turn (count[i] + 1 per stream: the last one is what follows the last delimiter).  keep_delim=False drops the
+        delimiter, trim_cr=True (only then) also one CR in front of it.  Returns (dst, dst_off, rec_len): uint8 and two int64 device
+        tensors.  stride=None: the records back to back, dst_off the exclusive prefix sum of rec_len (one scalar is read back for the
+        total).  stride=S: record j in dst[j * S .. (j + 1) * S), cut at S, the rest of its row zero; nothing is read back."""
+        import torch
+        if trim_cr and keep_delim:
+            raise BrxError("take_batch: trim_cr needs keep_delim=False")
+        n = int(out_len.numel())
+        if (sel_stream is None) != (sel_rec is None):
+            raise BrxError("take_batch: sel_stream and sel_rec go together")
+        hs = stream.cuda_stream if stream is not None else None
+        flags = (0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if sel_stream is not None:
+                sel_stream = sel_stream.to(torch.int32).contiguous()
+                sel_rec = sel_rec.to(torch.int64).contiguous()
+                m = int(sel_stream.numel())
+            else:
+                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
+            rec_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
+            rec_len = rec_buf[:m]
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        args = (out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(), pos_off.data_ptr(),
+                pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
+                sel_stream.data_ptr() if sel_stream is not None else None, sel_rec.data_ptr() if sel_rec is not None else None, m)
+        self.take_batch_device(*args, rec_buf.data_ptr(), hip_stream=hs)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if stride is None:
+                ends = torch.cumsum(rec_len, 0)
+                dst_off = ends - rec_len
+                total = int(ends[-1].item()) if m else 0  # (the read-back: waits for the size pass)
+                dst = torch.empty(max(total, 1), dtype=torch.uint8, device=out.device)
+            else:
+                dst_off = torch.arange(m, dtype=torch.int64, device=out.device) * int(stride)
+                total = m * int(stride)
+                dst = torch.zeros(max(total, 1), dtype=torch.uint8, device=out.device)
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()
+        if m:
+            self.take_batch_device(*args, None, dst_off.data_ptr(), dst.data_ptr(), total, hip_stream=hs)
+        return dst[:total], dst_off, rec_len
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

@@ -33,6 +33,7 @@
 #include "brx_index_quoted.h"
 #include "brx_index_escaped.h"
 #include "brx_find.h"
+#include "brx_take.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -1541,6 +1542,49 @@ extern "C" int brx_find_batch(brx_ctx *c, const uint8_t *needle, uint32_t needle
                         st);
         HIP_TRY(hipGetLastError());
         if ((rc = ring_record(c->find_ring, st)) != BRX_SUCCESS) return rc;
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- selected records of the decoded streams of a batch (brx_take.hip) ------------------------------------------------------
+extern "C" int brx_take_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                              const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                              uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t *rec_len,
+                              const uint64_t *dst_off, uint8_t *dst, uint64_t total, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: ctx is NULL");
+    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: unknown flag bits");
+    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
+    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: delim_len is not 1 .. 16");
+    if ((sel_stream == nullptr) != (sel_rec == nullptr))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: sel_stream and sel_rec go together");
+    if ((dst_off == nullptr) != (dst == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: dst_off and dst go together");
+    if (!dst && !rec_len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: rec_len is NULL in size mode");
+    if (m == 0) return BRX_SUCCESS;
+    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: NULL table");
+    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: pos is NULL with n_pos > 0");
+    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: all-records mode with n = 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: span out of range");
+    // the grids follow from m and total alone
+    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: m out of range");
+    if (dst && (total > (uint64_t)1 << 62 || brx_take_chunks(total, dst) > 0x7fffffffull))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: total out of range (more than 8 TiB)");
+    BrxTakeArgs a;
+    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
+    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
+    a.delim_len = delim_len; a.flags = flags;
+    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        if (rec_len) brx_launch_take_size(a, rec_len, st);
+        if (dst) brx_launch_take_fill(a, dst_off, dst, total, st);
+        HIP_TRY(hipGetLastError());
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
     return BRX_SUCCESS;

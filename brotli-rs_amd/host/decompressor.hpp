@@ -217,5 +217,17 @@ inline void find_batch(brx_ctx *ctx, const uint8_t *needle, uint32_t needle_len,
     if (brx_find_batch(ctx, needle, needle_len, out, out_off, len, n, span, count, pos_off, pos, total, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_find_batch: ") + brx_last_error());
 }
+// The selected records of the same batch, from the positions of any of the passes above (`delim_len` = 1, or the needle's length):
+// entry j is record sel_rec[j] of stream sel_stream[j], or with both nullptr every record of every stream in turn.  Size mode
+// (dst_off, dst nullptr): rec_len[j] = the record's length.  Fill mode: its bytes at dst[dst_off[j] ..], cut at the entry's room.
+// flags: BRX_TAKE_NO_DELIM, BRX_TAKE_TRIM_CR.
+inline void take_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                       const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                       uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t *rec_len,
+                       const uint64_t *dst_off = nullptr, uint8_t *dst = nullptr, uint64_t total = 0, void *stream = nullptr) {
+    if (brx_take_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m, rec_len,
+                       dst_off, dst, total, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_take_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

@@ -491,6 +491,64 @@ int brx_find_batch(brx_ctx *ctx, const uint8_t *needle, uint32_t needle_len,
                    const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                    void *hip_stream);
 
+/* ---- selected records of the decoded bytes of a batch, as lengths or as bytes (device memory only) --------
+ * The five passes above end at pos[], a list of offsets; what every consumer does next is take records: a data loader draws a
+ * shuffled sample and wants it packed back to back, a tokenizer wants every line in a fixed-stride row, a writer wants the batch
+ * without delimiters and without CRs.  This pass is that step: it takes the positions of any of the five passes plus a SELECTION of
+ * (stream, record) pairs and returns the records' lengths (size mode) or copies their bytes into a destination (fill mode).
+ * out, out_off, len, n and span are exactly as for brx_index_batch; nothing at or beyond out + span, or in front of out, is ever
+ * loaded.  count (n entries), pos_off (n entries, the exclusive prefix sum of count) and pos are what a fill-mode call of any of the
+ * five passes left behind, n_pos the number of entries pos holds.  All pointers are DEVICE memory.
+ * THE RULE.  Stream i is s = out[out_off[i] .. out_off[i] + len[i]); D = delim_len, 1 for the four index passes and needle_len for
+ * brx_find_batch, 1 <= D <= BRX_TAKE_MAX_DELIM = 16.  For 0 <= k < count[i]
+ *   P(i,k) = min(pos[pos_off[i] + k], len[i])  if pos_off[i] + k < n_pos,   else len[i] (pos is not loaded then)
+ * Record k of stream i exists for 0 <= k <= count[i]; record count[i] is the TRAILING one without a delimiter, empty when the stream
+ * ends on a delimiter.
+ *   start = 0 if k = 0, else min(P(i,k-1) + D, len[i])
+ *   end   = min(P(i,k) + D, len[i]) if k < count[i], else len[i]                       (no flags: the delimiter is part of the record)
+ *   end   = P(i,k)                  if k < count[i], else len[i]                       (BRX_TAKE_NO_DELIM)
+ *   end   = max(end, start)
+ *   BRX_TAKE_TRIM_CR: if end > start and s[end - 1] == 0x0D then end -= 1              (once; the trailing record too)
+ *   L     = end - start
+ * The clamps are part of the contract: stale, decreasing or garbage positions -- and the overlapping occurrences of a needle that
+ * overlaps itself -- yield short or empty records, never a load outside the stream and never a negative length.
+ * SELECTION.  Pairs mode (sel_stream and sel_rec both given, m entries each): entry j is record sel_rec[j] of stream sel_stream[j];
+ * with sel_stream[j] >= n or sel_rec[j] > count[sel_stream[j]] the entry selects nothing (L = 0).  Any order; a record may be named
+ * more than once.  All-records mode (both NULL): entry j is record j - (pos_off[i] + i) of stream i, the last stream with
+ * pos_off[i] + i <= j (every stream has count[i] + 1 records, so these keys are strictly increasing); an entry whose record index
+ * comes out above count[i] selects nothing; a consistent caller passes m = sum(count) + n.
+ * SIZE MODE (dst_off == NULL and dst == NULL; rec_len required): rec_len[j] = L_j for j < m.
+ * FILL MODE (dst_off and dst both given; rec_len may be NULL, and if given it is written as in size mode): dst_off has m entries and
+ * is non-decreasing; the ROOM of entry j is dst_off[j+1] - dst_off[j], for the last entry total - dst_off[m-1].
+ *   dst[dst_off[j] + t] = s[start_j + t]     for t < min(L_j, room_j)
+ * A record's bytes beyond its room are not written, a room's bytes beyond its record are left as they were, and no byte at index >=
+ * total is written.  With dst_off the exclusive prefix sum of rec_len the records come out back to back (the convention of
+ * brx_compact_batch); with dst_off[j] = j * stride every record sits in a row of its own, truncated at the stride.  Both follow from
+ * one rule: a destination byte belongs to the last entry whose dst_off is not behind it.  dst must not overlap the arena and needs
+ * no alignment.
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued (behind an
+ * index call on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.  No scratch, no
+ * upload, no read back: calls on different HIP streams may overlap without limit.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits; BRX_TAKE_TRIM_CR without
+ * BRX_TAKE_NO_DELIM; delim_len 0 or above 16; only one of sel_stream / sel_rec; only one of dst_off / dst; rec_len NULL in size mode;
+ * then m = 0 returns BRX_SUCCESS, no launch; then out_off, len, count or pos_off NULL; pos NULL with n_pos > 0; all-records mode with
+ * n = 0; span out of range (and m or total beyond what one launch addresses).
+ * Not in scope: decoding what a record means (unquoting, unescaping, number parsing); field selection within a record (index with
+ * ',' and take fields the same way); padding values other than "left as it was".
+ * Size mode reads the tables of the selected entries (and one byte per entry with BRX_TAKE_TRIM_CR) and writes 8 m; fill mode reads
+ * and writes the bytes taken, one pass; no reference counterpart. */
+#define BRX_TAKE_NO_DELIM 1u /* a record ends in front of its delimiter */
+#define BRX_TAKE_TRIM_CR  2u /* only with BRX_TAKE_NO_DELIM: then one trailing 0x0D is dropped as well */
+#define BRX_TAKE_MAX_DELIM 16u
+int brx_take_batch(brx_ctx *ctx,
+                   const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                   const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos,
+                   uint32_t delim_len, uint32_t flags,
+                   const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                   uint64_t *rec_len,
+                   const uint64_t *dst_off, uint8_t *dst, uint64_t total,
+                   void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one
