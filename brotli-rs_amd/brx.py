@@ -106,6 +106,11 @@ def load_library():
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint64, ctypes.c_void_p]
+    L.brx_hash_batch.restype = ctypes.c_int
+    L.brx_hash_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -162,7 +167,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
-                    "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch"]
+                    "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch"]
 
 
 def status_str(code: int) -> str:
@@ -570,6 +575,56 @@ class Context:
         if m:
             self.take_batch_device(*args, None, dst_off.data_ptr(), dst.data_ptr(), total, hip_stream=hs)
         return dst[:total], dst_off, rec_len
+
+    def hash_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
+                          sel_stream_ptr, sel_rec_ptr, m, seed, hash_ptr, rec_len_ptr=None, hip_stream=None):
+        """brx_hash_batch on raw device pointers: hash[j] = the 64-bit key of entry j of the selection under `seed`, the selection, the
+        positions and the flags exactly as for take_batch_device; rec_len (optional) as its size mode writes it."""
+        rc = self._lib.brx_hash_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len,
+                                      flags, sel_stream_ptr, sel_rec_ptr, m, int(seed) & 0xFFFFFFFFFFFFFFFF, hash_ptr, rec_len_ptr, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_hash_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def hash_batch(self, out, out_off, out_len, count, pos_off, pos, sel_stream=None, sel_rec=None, delim_len=1, keep_delim=True,
+                   trim_cr=False, seed=0, want_len=False, stream=None):
+        """A 64-bit key of every selected record of the decoded streams of a batch, computed on the device.  Every argument up to
+        trim_cr as for take_batch.  Returns an int64 device tensor (the 64-bit pattern of the hash that include/brx.h defines: equal
+        records get equal keys under one seed; the empty record gets 0), and with want_len=True the pair (hash, rec_len).  Nothing is
+        read back.  Exact de-duplication of the lines of a batch, the bytes copied once and only for the survivors:
+            count, _, pos_off, pos, _ = ctx.index_set_batch(out, out_off, out_len, delims=b"\\n", no_quote=True, no_escape=True)
+            key = ctx.hash_batch(out, out_off, out_len, count, pos_off, pos, keep_delim=False, trim_cr=True)
+            uniq, inverse = torch.unique(key, return_inverse=True)
+            first = torch.full_like(uniq, key.numel()).scatter_reduce_(0, inverse, torch.arange(key.numel(), device=key.device), "amin")
+            stream_of = torch.searchsorted(pos_off + torch.arange(pos_off.numel(), device=key.device), first, right=True) - 1
+            rec_of = first - (pos_off + torch.arange(pos_off.numel(), device=key.device))[stream_of]
+            dst, dst_off, rec_len = ctx.take_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=stream_of, sel_rec=rec_of,
+                                                   keep_delim=False, trim_cr=True)
+        (entry j of all-records mode is record j - (pos_off[i] + i) of stream i).  key % G shards the records over G workers."""
+        import torch
+        if trim_cr and keep_delim:
+            raise BrxError("hash_batch: trim_cr needs keep_delim=False")
+        n = int(out_len.numel())
+        if (sel_stream is None) != (sel_rec is None):
+            raise BrxError("hash_batch: sel_stream and sel_rec go together")
+        hs = stream.cuda_stream if stream is not None else None
+        flags = (0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if sel_stream is not None:
+                sel_stream = sel_stream.to(torch.int32).contiguous()
+                sel_rec = sel_rec.to(torch.int64).contiguous()
+                m = int(sel_stream.numel())
+            else:
+                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
+            hash_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
+            len_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device) if want_len else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        self.hash_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
+                               pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
+                               sel_stream.data_ptr() if sel_stream is not None else None,
+                               sel_rec.data_ptr() if sel_rec is not None else None, m, seed, hash_buf.data_ptr(),
+                               len_buf.data_ptr() if want_len else None, hip_stream=hs)
+        return (hash_buf[:m], len_buf[:m]) if want_len else hash_buf[:m]
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

@@ -34,6 +34,7 @@
 #include "brx_index_escaped.h"
 #include "brx_find.h"
 #include "brx_take.h"
+#include "brx_hash.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -1584,6 +1585,45 @@ extern "C" int brx_take_batch(brx_ctx *c, const uint8_t *out, const uint64_t *ou
         st = hip_stream ? (hipStream_t)hip_stream : c->stream;
         if (rec_len) brx_launch_take_size(a, rec_len, st);
         if (dst) brx_launch_take_fill(a, dst_off, dst, total, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- 64-bit keys of selected records of the decoded streams of a batch (brx_hash.hip) -----------------------------------------
+extern "C" int brx_hash_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                              const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                              uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t seed, uint64_t *hash,
+                              uint64_t *rec_len, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: ctx is NULL");
+    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: unknown flag bits");
+    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
+    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: delim_len is not 1 .. 16");
+    if ((sel_stream == nullptr) != (sel_rec == nullptr))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: sel_stream and sel_rec go together");
+    if (!hash) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: hash is NULL");
+    if (m == 0) return BRX_SUCCESS;
+    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: NULL table");
+    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: pos is NULL with n_pos > 0");
+    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: all-records mode with n = 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: span out of range");
+    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: m out of range"); // the grid follows from m alone
+    BrxTakeArgs a;
+    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
+    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
+    a.delim_len = delim_len; a.flags = flags;
+    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    const BrxHashKeys k = brx_hash_keys(seed); // K, K^2, K^3, K^4, K^256: launch arguments, no table
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        brx_launch_hash(a, k, hash, rec_len, st);
         HIP_TRY(hipGetLastError());
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));

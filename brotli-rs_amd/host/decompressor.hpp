@@ -229,5 +229,15 @@ inline void take_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off
                        dst_off, dst, total, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_take_batch: ") + brx_last_error());
 }
+// A 64-bit key of every selected record (the selection, the positions and the flags as for take_batch): hash[j] under `seed`, equal
+// for equal records, 0 for the empty one; rec_len (optional) as take_batch's size mode writes it.
+inline void hash_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                       const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                       uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t seed, uint64_t *hash,
+                       uint64_t *rec_len = nullptr, void *stream = nullptr) {
+    if (brx_hash_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m, seed, hash,
+                       rec_len, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_hash_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

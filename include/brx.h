@@ -549,6 +549,64 @@ int brx_take_batch(brx_ctx *ctx,
                    const uint64_t *dst_off, uint8_t *dst, uint64_t total,
                    void *hip_stream);
 
+/* ---- a 64-bit key of every selected record of the decoded bytes of a batch (device memory only) -----------
+ * What a consumer does with records is nearly always keyed on their content: exact de-duplication, hash partitioning (key % G),
+ * joins and membership tests.  This pass is the verb between "index" and "take": hash[j] is a 64-bit key of the bytes of entry j,
+ * and with it torch.unique / a sort gives the distinct records and brx_take_batch in pairs mode gathers exactly the survivors,
+ * without the bytes ever being copied in between.
+ * Every argument up to m means word for word what it means for brx_take_batch: the arena (out, out_off, len, n, span), the
+ * positions (count, pos_off, pos, n_pos), delim_len, THE RULE with all its clamps, the flags BRX_TAKE_NO_DELIM / BRX_TAKE_TRIM_CR
+ * (BRX_TAKE_TRIM_CR only with BRX_TAKE_NO_DELIM), pairs mode and all-records mode.  An entry that selects nothing is the empty
+ * record.  All pointers are DEVICE memory.  hash (m entries) is required; rec_len (m entries) is optional and, if given, is written
+ * exactly as the size mode of brx_take_batch writes it.  Nothing at or beyond out + span, or in front of out, is ever loaded.
+ * THE HASH, fixed here so that a CPU can reproduce it.  Arithmetic on non-negative integers, p = 2^61 - 1.
+ *   mix(x), on 64-bit words: x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *           (the splitmix64 finalizer: a bijection, mix(0) = 0)
+ *   K(seed) = 2 + mix((seed + 0x9E3779B97F4A7C15) mod 2^64) mod (p - 3)
+ * For a record r[0 .. L):  U = ceil(L / 4);  c_u = the little-endian 32-bit word of r[4u .. 4u + 4), bytes at or behind L taken as 0
+ * (where those bytes lie outside the record's stream they are never loaded);
+ *   h(r)  = ( L + sum_{u < U} c_u * K^(U - u) ) mod p,  in [0, p)
+ *   hash  = mix(h(r))
+ * The empty record hashes to 0.
+ * Equal records (same bytes, same length) get equal hashes under one seed, wherever they lie and at whatever alignment.  Two
+ * different records of at most Lmax bytes collide with probability at most ceil(Lmax / 4) / p over the choice of seed: they are
+ * different polynomials in K of degree at most ceil(Lmax / 4), because the constant term carries L (and mix is a bijection).  For a
+ * batch of 14.8 M records of at most 128 bytes (4096 x alice29 by lines) the bound over all 1.1e14 pairs is 1.1e14 * 32 / 2.3e18 =
+ * 1.5e-3 that ANY two different records share a key; a caller that needs more calls twice with two seeds (122 bits, 2e-20 for
+ * that batch) or confirms with the bytes.  The hash is not cryptographic -- whoever knows the seed can construct collisions -- and
+ * it is not stable across different seeds.
+ * Composition law (the kernel relies on it; so may a caller who joins keys of pieces): with S(r) = h(r) - L and A a whole number
+ * of words,  S(A || B) = S(A) * K^(U_B) + S(B)  (mod p).
+ * Check values (hash; K first):
+ *   seed 0:        K = 0x220a8397b1dcdcd    "a" 0xba350051cabf3ed3   "a\0" 0xbb6016563a245eba   "abcd" 0xada6cd48c13c1c39
+ *                  "abcde" 0xf35fc97551548103   "hello, world\n" 0x0be5baf8a63cf33d   bytes 0..255 0x5bb278495e403ce2
+ *                  before mix: h("a") = 0x0e5fbdc7a64afab4, h("abcd") = 0x1117ffd3c0071df7
+ *   seed 1:        K = 0x110a2dec89025cd3   "a" 0x4d210b0efb807995   "a\0" 0x201b4b401d4bfd95   "abcd" 0x48e414395e8656fd
+ *                  "abcde" 0x78061f9a959b2150   "hello, world\n" 0x6879e40593ee90c8   bytes 0..255 0x4540b5719777dafd
+ *   seed 2^64 - 1: K = 0x4d971771b652c3e    "a" 0xc98a66ada32c9c2d   "abcd" 0x5032cab1b617812b
+ *                  "hello, world\n" 0x4e8c2d5bfbc9d732   bytes 0..255 0x0bc6190075701881
+ * With count all zero, n_pos = 0, all-records mode and m = n, entry i is the whole of stream i: whole-stream keys need no other call.
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued (behind an
+ * index call on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.  No scratch, no
+ * upload, no read back: calls on different HIP streams may overlap without limit.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits; BRX_TAKE_TRIM_CR without
+ * BRX_TAKE_NO_DELIM; delim_len 0 or above 16; only one of sel_stream / sel_rec; hash NULL; then m = 0 returns BRX_SUCCESS, no
+ * launch; then out_off, len, count or pos_off NULL; pos NULL with n_pos > 0; all-records mode with n = 0; span out of range (and m
+ * beyond what one launch addresses).
+ * Not in scope: other hash functions (xxHash, FNV, a CRC per record, whose 32 bits are too few for de-duplication); case folding or
+ * normalisation before hashing; the de-duplication itself (torch.unique or a sort over the keys); hashing fields within records
+ * (index with ',' and hash those the same way).
+ * Reads the tables of the selected entries and every byte of their records once, writes 8 m (16 m with rec_len); one launch; no
+ * reference counterpart. */
+int brx_hash_batch(brx_ctx *ctx,
+                   const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                   const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos,
+                   uint32_t delim_len, uint32_t flags,
+                   const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                   uint64_t seed,
+                   uint64_t *hash, uint64_t *rec_len,
+                   void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one
