@@ -29,6 +29,13 @@ INDEX_NO_QUOTE = 1  # BRX_INDEX_NO_QUOTE
 INDEX_NO_ESCAPE = 2  # BRX_INDEX_NO_ESCAPE (brx_index_set_batch only)
 TAKE_NO_DELIM = 1  # BRX_TAKE_NO_DELIM
 TAKE_TRIM_CR = 2  # BRX_TAKE_TRIM_CR (only with TAKE_NO_DELIM)
+PARSE_SPACES = 16  # BRX_PARSE_SPACES (brx_parse_batch only, in the same flags word)
+PARSE_QUOTED = 32  # BRX_PARSE_QUOTED
+PARSE_INT, PARSE_DEC, PARSE_HEX = 0, 1, 2  # BRX_PARSE_INT / _DEC / _HEX
+PARSE_KINDS = {"int": PARSE_INT, "dec": PARSE_DEC, "hex": PARSE_HEX}
+PARSE_OK, PARSE_INEXACT, PARSE_EMPTY, PARSE_RANGE, PARSE_BAD, PARSE_LONG = 0, 1, 2, 3, 4, 5  # BRX_PARSE_OK ... (the status byte)
+PARSE_MAX_LEN = 64  # BRX_PARSE_MAX_LEN
+PARSE_MAX_SCALE = 18  # BRX_PARSE_MAX_SCALE
 
 
 class BrxError(RuntimeError):
@@ -111,6 +118,11 @@ def load_library():
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_void_p]
+    L.brx_parse_batch.restype = ctypes.c_int
+    L.brx_parse_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -167,7 +179,8 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_ctx_set_option", "brx_last_trace", "brx_stream_new_reader", "brx_node_create", "brx_node_destroy",
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
-                    "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch"]
+                    "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch",
+                    "brx_parse_batch"]
 
 
 def status_str(code: int) -> str:
@@ -625,6 +638,60 @@ class Context:
                                sel_rec.data_ptr() if sel_rec is not None else None, m, seed, hash_buf.data_ptr(),
                                len_buf.data_ptr() if want_len else None, hip_stream=hs)
         return (hash_buf[:m], len_buf[:m]) if want_len else hash_buf[:m]
+
+    def parse_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
+                           sel_stream_ptr, sel_rec_ptr, m, kind, scale, quote, val_ptr, status_ptr, hip_stream=None):
+        """brx_parse_batch on raw device pointers: val[j] (int64) = the number that entry j of the selection spells, status[j] (uint8) =
+        PARSE_OK .. PARSE_LONG; the selection, the positions and the TAKE_* flags exactly as for take_batch_device, PARSE_SPACES /
+        PARSE_QUOTED in the same flags word; kind PARSE_INT / PARSE_DEC / PARSE_HEX, scale 0 .. 18 (PARSE_DEC only), quote a byte value."""
+        rc = self._lib.brx_parse_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len,
+                                       flags, sel_stream_ptr, sel_rec_ptr, m, kind, scale, quote, val_ptr, status_ptr, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_parse_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def parse_batch(self, out, out_off, out_len, count, pos_off, pos, sel_stream=None, sel_rec=None, delim_len=1, keep_delim=False,
+                    trim_cr=False, kind="int", scale=0, spaces=False, quote=None, stream=None):
+        """Every selected record of the decoded streams of a batch as a 64-bit number, parsed on the device.  Every argument up to
+        trim_cr as for take_batch -- except that keep_delim defaults to False here, because a number never contains its delimiter (with
+        keep_delim=True every record that has one comes out PARSE_BAD).  kind: "int" ([+-]? digits), "dec" (digits with an optional
+        point; the value is x * 10**scale truncated toward zero, scale 0 .. 18) or "hex" (an optional 0x / 0X, then hex digits, no
+        sign).  spaces=True drops leading and trailing blanks and tabs; quote=b'"' then drops one enclosing pair of that byte
+        (quote=None: no unquoting).  Returns (val, status): an int64 and a uint8 device tensor, status[j] one of PARSE_OK,
+        PARSE_INEXACT (a non-zero fraction digit was cut off), PARSE_EMPTY (nothing there: a missing value), PARSE_RANGE (outside 64
+        bits: val is the nearest bound, all ones for hex), PARSE_BAD (not such a number) and PARSE_LONG (a record above 64 bytes,
+        not looked at); val is 0 for EMPTY, BAD and LONG.  Nothing is read back.  The prices of a CSV batch, in cents:
+            count, _, pos_off, pos, _ = ctx.index_set_batch(out, out_off, out_len, delims=b",\n", no_quote=True, no_escape=True)
+            val, status = ctx.parse_batch(out, out_off, out_len, count, pos_off, pos, trim_cr=True, kind="dec", scale=2)"""
+        import torch
+        if trim_cr and keep_delim:
+            raise BrxError("parse_batch: trim_cr needs keep_delim=False")
+        if kind not in PARSE_KINDS:
+            raise BrxError("parse_batch: kind is one of %s" % ", ".join(sorted(PARSE_KINDS)))
+        if quote is not None and len(bytes(quote)) != 1:
+            raise BrxError("parse_batch: quote is one byte, or None")
+        n = int(out_len.numel())
+        if (sel_stream is None) != (sel_rec is None):
+            raise BrxError("parse_batch: sel_stream and sel_rec go together")
+        hs = stream.cuda_stream if stream is not None else None
+        flags = ((0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
+                 | (PARSE_QUOTED if quote is not None else 0))
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if sel_stream is not None:
+                sel_stream = sel_stream.to(torch.int32).contiguous()
+                sel_rec = sel_rec.to(torch.int64).contiguous()
+                m = int(sel_stream.numel())
+            else:
+                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
+            val_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
+            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        self.parse_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
+                                pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
+                                sel_stream.data_ptr() if sel_stream is not None else None,
+                                sel_rec.data_ptr() if sel_rec is not None else None, m, PARSE_KINDS[kind], int(scale),
+                                bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
+        return val_buf[:m], status_buf[:m]
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

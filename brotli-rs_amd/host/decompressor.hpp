@@ -239,5 +239,16 @@ inline void hash_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off
                        rec_len, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_hash_batch: ") + brx_last_error());
 }
+// Every selected record as a 64-bit number (the selection, the positions and the BRX_TAKE_* flags as for take_batch; BRX_PARSE_SPACES /
+// BRX_PARSE_QUOTED in the same flags word): val[j] and status[j] (BRX_PARSE_OK .. BRX_PARSE_LONG) for `kind` BRX_PARSE_INT, BRX_PARSE_DEC
+// (x * 10^scale truncated toward zero, scale 0 .. 18) or BRX_PARSE_HEX.  Exact integer arithmetic; records above 64 bytes are LONG.
+inline void parse_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                        const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                        uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint32_t kind, uint32_t scale,
+                        uint8_t quote, int64_t *val, uint8_t *status, void *stream = nullptr) {
+    if (brx_parse_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m, kind, scale,
+                        quote, val, status, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_parse_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

@@ -607,6 +607,79 @@ int brx_hash_batch(brx_ctx *ctx,
                    uint64_t *hash, uint64_t *rec_len,
                    void *hip_stream);
 
+/* ---- every selected record of the decoded bytes of a batch as a 64-bit number (device memory only) --------
+ * With delims = ",\n" every field of a table is a record, and most fields of a table or a log are numbers.  This pass is the step
+ * behind "index": val[j] is the number that entry j of a selection spells and status[j] says whether it spelled one, straight from
+ * the arena -- no bytes gathered, nothing read back, and all of it exact integer arithmetic that a CPU reproduces bit for bit.
+ * Every argument up to m means word for word what it means for brx_take_batch / brx_hash_batch: the arena (out, out_off, len, n,
+ * span), the positions (count, pos_off, pos, n_pos), delim_len, THE RULE with all its clamps, the flags BRX_TAKE_NO_DELIM /
+ * BRX_TAKE_TRIM_CR (BRX_TAKE_TRIM_CR only with BRX_TAKE_NO_DELIM), pairs mode and all-records mode.  An entry that selects nothing
+ * is the empty record.  All pointers are DEVICE memory.  val and status (m entries each) are both required.  Nothing at or beyond
+ * out + span, or in front of out, is ever loaded.
+ * Two more bits of the same flags word: BRX_PARSE_SPACES, BRX_PARSE_QUOTED.  kind: BRX_PARSE_INT, BRX_PARSE_DEC, BRX_PARSE_HEX.
+ * scale: 0 .. BRX_PARSE_MAX_SCALE = 18 for BRX_PARSE_DEC, 0 for the other two.  status[j] is one of BRX_PARSE_OK .. BRX_PARSE_LONG.
+ * THE PARSE, for the record r[0 .. L) that the rule gives (after BRX_TAKE_TRIM_CR):
+ *   1. L > BRX_PARSE_MAX_LEN = 64: LONG, val = 0.  None of the record's bytes is loaded (beyond the one BRX_TAKE_TRIM_CR looks at):
+ *      every entry's work is bounded, and whole streams as records are harmless.
+ *   2. With BRX_PARSE_SPACES: leading and trailing bytes 0x20 and 0x09 are dropped.
+ *   3. With BRX_PARSE_QUOTED: if at least 2 bytes remain and the first and the last both equal `quote`, both are dropped -- once;
+ *      spaces inside the quotes are not dropped.  Without the flag `quote` is ignored.
+ *   4. What remains is t[0 .. T).  T = 0: EMPTY, val = 0 (a missing value, distinct from BAD).
+ *   5. Grammar, matched against all of t, D = 0-9, H = 0-9a-fA-F:
+ *        INT  [+-]? D+          DEC  [+-]? ( D+ ( '.' D* )? | '.' D+ )          HEX  ( '0' [xX] )? H+
+ *      No exponent, no digit separators, no inf / nan.  A mismatch: BAD, val = 0.
+ *   6. INT / DEC: with I the integer digits (none: 0) and F the fraction digits, V = sign * (I followed by the first `scale` digits of
+ *      F, padded with '0' up to `scale` digits) read as a decimal integer of unbounded size: x * 10^scale truncated toward zero.
+ *      V > 2^63 - 1: RANGE, val = INT64_MAX.  V < -2^63: RANGE, val = INT64_MIN.  Otherwise val = V, and the status is INEXACT if
+ *      any digit of F behind the first `scale` is not '0', else OK.  RANGE wins over INEXACT.  Any number of leading zeros is
+ *      allowed (the bound is the 64 bytes, not a digit count); -0 is 0.
+ *   7. HEX: V = the value of the H digits.  V >= 2^64: RANGE, val = all ones.  Otherwise val = the 64-bit pattern of V, OK.  No sign.
+ * Check values, val / status, MAX = 9223372036854775807, MIN = -9223372036854775808:
+ *   INT:  "0" 0 / OK   "-0" 0 / OK   "+17" 17 / OK   "9223372036854775807" MAX / OK   "9223372036854775808" MAX / RANGE
+ *         "-9223372036854775808" MIN / OK   "-9223372036854775809" MIN / RANGE   45 zeros + "9223372036854775807" (64 bytes) MAX / OK
+ *         the same with 46 zeros (65 bytes) 0 / LONG   "12.5" 0 / BAD   "" 0 / EMPTY   "-" 0 / BAD   "1 " 0 / BAD
+ *   DEC, scale 2:  "12.34" 1234 / OK   "12.345" 1234 / INEXACT   "12.340" 1234 / OK   "-.5" -50 / OK   "5." 500 / OK   "." 0 / BAD
+ *         "-0.009" 0 / INEXACT   "1e3" 0 / BAD   "92233720368547758.07" MAX / OK   "92233720368547758.08" MAX / RANGE
+ *         "-92233720368547758.089" MIN / INEXACT
+ *   DEC, scale 0:  "12.5" 12 / INEXACT.      DEC, scale 18:  "9.223372036854775807" MAX / OK   "9.3" MAX / RANGE
+ *   HEX:  "ff" 255 / OK   "0xFFFFFFFFFFFFFFFF" all ones / OK   "0x10000000000000000" all ones / RANGE   "0x" 0 / BAD   "x1" 0 / BAD
+ *         "0X0000000000000000000000001f" 31 / OK
+ *   INT with BRX_PARSE_SPACES | BRX_PARSE_QUOTED, quote '"' (the text between the brackets):
+ *         [ "42"\t] 42 / OK   [" 42"] 0 / BAD   ["42] 0 / BAD   ["] 0 / BAD   [""] 0 / EMPTY   [two spaces] 0 / EMPTY
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued (behind an
+ * index call on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.  No scratch, no
+ * upload, no read back, one launch: calls on different HIP streams may overlap without limit.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits; BRX_TAKE_TRIM_CR without
+ * BRX_TAKE_NO_DELIM; delim_len 0 or above 16; only one of sel_stream / sel_rec; kind above 2; scale above 18, or non-zero with
+ * BRX_PARSE_INT / BRX_PARSE_HEX; val or status NULL; then m = 0 returns BRX_SUCCESS, no launch; then out_off, len, count or pos_off
+ * NULL; pos NULL with n_pos > 0; all-records mode with n = 0; span out of range (and m beyond what one launch addresses).
+ * Not in scope: binary floating point (a correctly rounded double needs a power-of-ten table and a slow path: the named follow-up;
+ * BRX_PARSE_DEC with a scale is the exact substitute); exponents, thousands separators, locale decimal commas; dates and times;
+ * unescaping; records above 64 bytes.
+ * Reads the tables of the selected entries and every byte of their records of at most 64 bytes once, writes 9 m; one launch; no
+ * reference counterpart. */
+#define BRX_PARSE_SPACES 16u /* leading and trailing 0x20 / 0x09 are dropped */
+#define BRX_PARSE_QUOTED 32u /* then one pair of enclosing `quote` bytes is dropped */
+#define BRX_PARSE_INT 0u
+#define BRX_PARSE_DEC 1u
+#define BRX_PARSE_HEX 2u
+#define BRX_PARSE_MAX_SCALE 18u
+#define BRX_PARSE_MAX_LEN 64u
+#define BRX_PARSE_OK      0u
+#define BRX_PARSE_INEXACT 1u /* DEC: a non-zero digit behind the first `scale` fraction digits was cut off */
+#define BRX_PARSE_EMPTY   2u /* nothing to parse: a missing value */
+#define BRX_PARSE_RANGE   3u /* a number, but outside 64 bits: val is the nearest bound */
+#define BRX_PARSE_BAD     4u /* not a number of this kind */
+#define BRX_PARSE_LONG    5u /* a record above BRX_PARSE_MAX_LEN bytes: not looked at */
+int brx_parse_batch(brx_ctx *ctx,
+                    const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                    const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos,
+                    uint32_t delim_len, uint32_t flags,
+                    const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                    uint32_t kind, uint32_t scale, uint8_t quote,
+                    int64_t *val, uint8_t *status,
+                    void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one
