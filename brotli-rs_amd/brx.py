@@ -36,6 +36,8 @@ PARSE_KINDS = {"int": PARSE_INT, "dec": PARSE_DEC, "hex": PARSE_HEX}
 PARSE_OK, PARSE_INEXACT, PARSE_EMPTY, PARSE_RANGE, PARSE_BAD, PARSE_LONG = 0, 1, 2, 3, 4, 5  # BRX_PARSE_OK ... (the status byte)
 PARSE_MAX_LEN = 64  # BRX_PARSE_MAX_LEN
 PARSE_MAX_SCALE = 18  # BRX_PARSE_MAX_SCALE
+PARSE_WORDS = 64  # BRX_PARSE_WORDS (brx_parse_f64_batch only)
+PARSE_HARD = 6  # BRX_PARSE_HARD (brx_parse_f64_batch only: val or the next double away from zero)
 
 
 class BrxError(RuntimeError):
@@ -123,6 +125,11 @@ def load_library():
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.brx_parse_f64_batch.restype = ctypes.c_int
+    L.brx_parse_f64_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -181,6 +188,10 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
                     "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch",
                     "brx_parse_batch"]
+# Exported names with a digit in them.  They are kept apart because tests/test_abi.py compares EXPORTED_SYMBOLS with the names it reads
+# from include/brx.h by the pattern brx_[a-z_]+, which such a name does not match; tests/test_parse_f64_abi.py holds this list to the
+# header and to the library.
+EXPORTED_SYMBOLS_NUMBERED = ["brx_parse_f64_batch"]
 
 
 def status_str(code: int) -> str:
@@ -692,6 +703,93 @@ class Context:
                                 sel_rec.data_ptr() if sel_rec is not None else None, m, PARSE_KINDS[kind], int(scale),
                                 bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
         return val_buf[:m], status_buf[:m]
+
+    def parse_f64_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
+                               sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream=None):
+        """brx_parse_f64_batch on raw device pointers: val[j] (binary64) = the correctly rounded double that entry j of the selection
+        spells, status[j] (uint8) = PARSE_OK, PARSE_EMPTY, PARSE_RANGE, PARSE_BAD, PARSE_LONG or PARSE_HARD; the selection, the positions
+        and the TAKE_* flags exactly as for take_batch_device, PARSE_SPACES / PARSE_QUOTED / PARSE_WORDS in the same flags word; quote
+        a byte value."""
+        rc = self._lib.brx_parse_f64_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos,
+                                           delim_len, flags, sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_parse_f64_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def parse_f64_batch(self, out, out_off, out_len, count, pos_off, pos, sel_stream=None, sel_rec=None, delim_len=1, keep_delim=False,
+                        trim_cr=False, spaces=False, quote=None, words=False, finish=False, stream=None):
+        """Every selected record of the decoded streams of a batch as a correctly rounded double, parsed on the device.  Every argument
+        up to trim_cr as for parse_batch (keep_delim defaults to False: a number never contains its delimiter).  The grammar is
+        [+-]? digits with an optional point, then an optional e / E exponent; words=True also takes [+-]? nan / inf / infinity in any
+        letter case.  spaces=True drops leading and trailing blanks and tabs; quote=b'"' then drops one enclosing pair of that byte.
+        Returns (val, status): a torch.float64 and a torch.uint8 device tensor, status[j] one of PARSE_OK, PARSE_EMPTY (nothing there),
+        PARSE_RANGE (beyond the largest double: val is +-inf; or non-zero and rounded to +-0), PARSE_BAD (not such a number),
+        PARSE_LONG (a record above 64 bytes, not looked at) and PARSE_HARD (more than 19 significant digits and too close to a
+        rounding boundary for the device: the correctly rounded double is val or the next one away from zero); val is +0 for EMPTY,
+        BAD and LONG.  Text printed with up to 17 digits never comes out PARSE_HARD.
+        finish=True completes the PARSE_HARD entries on the host: their (stream, record) pairs are derived (in all-records mode from
+        pos_off, as the device derives them), their bytes fetched with take_batch in pairs mode, trimmed as the call trims, converted
+        with float() and written back with status PARSE_OK or PARSE_RANGE.  It synchronises and reads back one flag, and the bytes
+        only when some entry is PARSE_HARD; with finish=False nothing is read back.  The measurements of a CSV batch:
+            count, _, pos_off, pos, _ = ctx.index_set_batch(out, out_off, out_len, delims=b",\\n", no_quote=True, no_escape=True)
+            val, status = ctx.parse_f64_batch(out, out_off, out_len, count, pos_off, pos, trim_cr=True, finish=True)"""
+        import torch
+        if trim_cr and keep_delim:
+            raise BrxError("parse_f64_batch: trim_cr needs keep_delim=False")
+        if quote is not None and len(bytes(quote)) != 1:
+            raise BrxError("parse_f64_batch: quote is one byte, or None")
+        n = int(out_len.numel())
+        if (sel_stream is None) != (sel_rec is None):
+            raise BrxError("parse_f64_batch: sel_stream and sel_rec go together")
+        hs = stream.cuda_stream if stream is not None else None
+        flags = ((0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
+                 | (PARSE_QUOTED if quote is not None else 0) | (PARSE_WORDS if words else 0))
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if sel_stream is not None:
+                sel_stream = sel_stream.to(torch.int32).contiguous()
+                sel_rec = sel_rec.to(torch.int64).contiguous()
+                m = int(sel_stream.numel())
+            else:
+                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
+            val_buf = torch.empty(max(m, 1), dtype=torch.float64, device=out.device)  # (an empty view has no address)
+            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        self.parse_f64_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
+                                    pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
+                                    sel_stream.data_ptr() if sel_stream is not None else None,
+                                    sel_rec.data_ptr() if sel_rec is not None else None, m,
+                                    bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
+        val, status = val_buf[:m], status_buf[:m]
+        if not finish or m == 0:
+            return val, status
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            hard = torch.nonzero(status == PARSE_HARD).flatten()
+            k = int(hard.numel())  # (the read-back: waits for the parse)
+            if k == 0:
+                return val, status
+            if sel_stream is not None:
+                h_stream, h_rec = sel_stream[hard], sel_rec[hard]
+            else:  # entry j is record j - (pos_off[i] + i) of stream i, the last stream with pos_off[i] + i <= j
+                keys = pos_off.to(torch.int64) + torch.arange(n, dtype=torch.int64, device=out.device)
+                h_stream = torch.searchsorted(keys, hard, right=True) - 1
+                h_rec = hard - keys[h_stream]
+        rows, _, rec_len = self.take_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=h_stream, sel_rec=h_rec,
+                                           delim_len=delim_len, keep_delim=keep_delim, trim_cr=trim_cr, stride=PARSE_MAX_LEN, stream=stream)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            rows, rec_len = rows.cpu().numpy().reshape(k, PARSE_MAX_LEN), rec_len.cpu().tolist()
+            new_val, new_status = [], []
+            for row, ln in zip(rows, rec_len):
+                t = row[:ln].tobytes()
+                if spaces:
+                    t = t.strip(b" \t")
+                if quote is not None and len(t) >= 2 and t[:1] == bytes(quote) and t[-1:] == bytes(quote):
+                    t = t[1:-1]
+                x = float(t.decode("ascii"))  # correctly rounded; a PARSE_HARD entry is a number of the grammar
+                new_val.append(x)
+                new_status.append(PARSE_RANGE if x == 0.0 or x in (float("inf"), float("-inf")) else PARSE_OK)
+            val[hard] = torch.tensor(new_val, dtype=torch.float64).to(out.device)
+            status[hard] = torch.tensor(new_status, dtype=torch.uint8).to(out.device)
+        return val, status
 
     def last_timing_ms(self, which=1):
         return float(self._lib.brx_last_timing(self._h, which))

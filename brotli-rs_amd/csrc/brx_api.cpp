@@ -36,6 +36,7 @@
 #include "brx_take.h"
 #include "brx_hash.h"
 #include "brx_parse.h"
+#include "brx_parse_f64.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -1667,6 +1668,45 @@ extern "C" int brx_parse_batch(brx_ctx *c, const uint8_t *out, const uint64_t *o
         HIP_TRY(hipSetDevice(c->device));
         st = hip_stream ? (hipStream_t)hip_stream : c->stream;
         brx_launch_parse(a, kind, scale, quote, val, status, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- selected records of the decoded streams of a batch as correctly rounded doubles (brx_parse_f64.hip) ---------------------
+extern "C" int brx_parse_f64_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                                   const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                                   uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint8_t quote, double *val,
+                                   uint8_t *status, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: ctx is NULL");
+    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | BRX_PARSE_SPACES | BRX_PARSE_QUOTED | BRX_PARSE_WORDS))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: unknown flag bits");
+    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
+    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: delim_len is not 1 .. 16");
+    if ((sel_stream == nullptr) != (sel_rec == nullptr))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: sel_stream and sel_rec go together");
+    if (!val || !status) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: val or status is NULL");
+    if (m == 0) return BRX_SUCCESS;
+    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: NULL table");
+    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: pos is NULL with n_pos > 0");
+    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: all-records mode with n = 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: span out of range");
+    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: m out of range"); // the grid follows from m alone
+    BrxTakeArgs a;
+    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
+    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
+    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the parse its own three)
+    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        brx_launch_parse_f64(a, quote, (uint64_t *)val, status, st); // (the kernel writes bit patterns: no double arithmetic on the device)
         HIP_TRY(hipGetLastError());
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));

@@ -250,5 +250,16 @@ inline void parse_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_of
                         quote, val, status, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_parse_batch: ") + brx_last_error());
 }
+// Every selected record as a correctly rounded double (the selection, the positions and the BRX_TAKE_* flags as for take_batch;
+// BRX_PARSE_SPACES / BRX_PARSE_QUOTED / BRX_PARSE_WORDS in the same flags word): val[j] and status[j] (BRX_PARSE_OK, _EMPTY, _RANGE, _BAD,
+// _LONG, or _HARD: val[j] or the next double away from zero, to be finished by the caller).  Exponents; records above 64 bytes are LONG.
+inline void parse_f64_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                            const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                            uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint8_t quote, double *val,
+                            uint8_t *status, void *stream = nullptr) {
+    if (brx_parse_f64_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m, quote, val,
+                            status, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_parse_f64_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

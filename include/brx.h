@@ -655,7 +655,7 @@ int brx_hash_batch(brx_ctx *ctx,
  * NULL; pos NULL with n_pos > 0; all-records mode with n = 0; span out of range (and m beyond what one launch addresses).
  * Not in scope: binary floating point (a correctly rounded double needs a power-of-ten table and a slow path: the named follow-up;
  * BRX_PARSE_DEC with a scale is the exact substitute); exponents, thousands separators, locale decimal commas; dates and times;
- * unescaping; records above 64 bytes.
+ * unescaping; records above 64 bytes.  (The follow-up is brx_parse_f64_batch below: doubles, with exponents, as a call of its own.)
  * Reads the tables of the selected entries and every byte of their records of at most 64 bytes once, writes 9 m; one launch; no
  * reference counterpart. */
 #define BRX_PARSE_SPACES 16u /* leading and trailing 0x20 / 0x09 are dropped */
@@ -679,6 +679,78 @@ int brx_parse_batch(brx_ctx *ctx,
                     uint32_t kind, uint32_t scale, uint8_t quote,
                     int64_t *val, uint8_t *status,
                     void *hip_stream);
+
+/* ---- every selected record of the decoded bytes of a batch as a correctly rounded double (device memory only) --------
+ * The numeric columns that brx_parse_batch stops short of: "3.25", "1e-7", "6.02E23".  val[j] is the binary64 that entry j of a
+ * selection spells and status[j] says whether it spelled one, straight from the arena -- no bytes gathered, nothing read back, integer
+ * arithmetic only, so that a CPU reproduces every bit and every status.
+ * Every argument up to m means word for word what it means for brx_take_batch / brx_hash_batch / brx_parse_batch: the arena (out,
+ * out_off, len, n, span), the positions (count, pos_off, pos, n_pos), delim_len, THE RULE with all its clamps, the flags
+ * BRX_TAKE_NO_DELIM / BRX_TAKE_TRIM_CR (BRX_TAKE_TRIM_CR only with BRX_TAKE_NO_DELIM), pairs mode and all-records mode.  An entry that
+ * selects nothing is the empty record.  All pointers are DEVICE memory.  val and status (m entries each) are both required.  Nothing
+ * at or beyond out + span, or in front of out, is ever loaded.
+ * Three more bits of the same flags word: BRX_PARSE_SPACES, BRX_PARSE_QUOTED and BRX_PARSE_WORDS (this call only: brx_parse_batch
+ * refuses it).  status[j] is one of BRX_PARSE_OK, _EMPTY, _RANGE, _BAD, _LONG, _HARD.  val is given below as a bit pattern; +0 is
+ * 0x0000000000000000.
+ * THE PARSE, F64, for the record r[0 .. L) that the rule gives (after BRX_TAKE_TRIM_CR); steps 1 - 4 are those of brx_parse_batch:
+ *   1. L > BRX_PARSE_MAX_LEN = 64: LONG, val = +0.  None of the record's bytes is loaded (beyond the one BRX_TAKE_TRIM_CR looks at).
+ *   2. With BRX_PARSE_SPACES: leading and trailing bytes 0x20 and 0x09 are dropped.
+ *   3. With BRX_PARSE_QUOTED: if at least 2 bytes remain and the first and the last both equal `quote`, both are dropped -- once.
+ *      Without the flag `quote` is ignored.
+ *   4. What remains is t[0 .. T).  T = 0: EMPTY, val = +0.
+ *   5. Grammar, matched against all of t, D = 0-9:   [+-]? ( D+ ( '.' D* )? | '.' D+ ) ( [eE] [+-]? D+ )?
+ *      With BRX_PARSE_WORDS also [+-]? followed by nan, inf or infinity in any letter case: status OK, val = 0x7FF8000000000000 for nan,
+ *      0x7FF0000000000000 for the other two, bit 63 set behind a '-'.  Without the flag those words are BAD.  No hex float, no digit
+ *      separator, no locale comma.  A mismatch: BAD, val = +0.
+ *   6. Value: x = the exact rational value of the text; any number of leading zeros anywhere, the exponent's digits included (the
+ *      bound is the 64 bytes).  val = x rounded to binary64, round to nearest, ties to even, subnormals included, with the sign of the
+ *      text: "-0" is 0x8000000000000000 (unlike INT).  An x that rounds beyond the largest finite double: +-inf, RANGE.  A non-zero x
+ *      that rounds to +-0: +-0, RANGE.  Everything else OK.
+ *   7. The bound on a lane's work.  s = the digits of the integer and the fraction part together, leading zeros stripped.  At most 19
+ *      digits, or nothing but '0' behind the 19th: never HARD.  Otherwise w = the first 19 digits and q the power of ten with
+ *      w * 10^q < |x| < (w + 1) * 10^q; a = RN(w * 10^q), b = RN((w + 1) * 10^q).  a = b: val = a under step 6's statuses (rounding
+ *      is monotone).  a != b: status HARD, val = a with the text's sign; HARD wins over RANGE.  The correctly rounded result is then val
+ *      or the next double away from zero, the bit pattern plus 1 (w >= 10^18, so a and b are neighbours).  The status is a function
+ *      of the text alone: the caller knows exactly which entries to finish elsewhere.  Text printed with up to 17 digits never meets
+ *      it; of random numbers of 20 - 40 digits about one in 600 does.
+ * Check values, val (hex) / status:
+ *   "0" 0000000000000000 / OK   "-0" 8000000000000000 / OK   "1" 3FF0000000000000 / OK   "-1.5" BFF8000000000000 / OK
+ *   "0.1" 3FB999999999999A / OK   ".5" 3FE0000000000000 / OK   "5." 4014000000000000 / OK   "1e23" 44B52D02C7E14AF6 / OK
+ *   "1E+2" 4059000000000000 / OK   "1e-2" 3F847AE147AE147B / OK   "9007199254740993" 4340000000000000 / OK
+ *   "9007199254740995" 4340000000000002 / OK   "1.7976931348623157e308" 7FEFFFFFFFFFFFFF / OK
+ *   "1.7976931348623158e308" 7FEFFFFFFFFFFFFF / OK   "1.7976931348623159e308" 7FF0000000000000 / RANGE
+ *   "-1e309" FFF0000000000000 / RANGE   "4.9e-324" 0000000000000001 / OK   "2.4703282292062328e-324" 0000000000000001 / OK
+ *   "2.4703282292062327e-324" 0000000000000000 / RANGE   "1e-400" 0000000000000000 / RANGE
+ *   "2.2250738585072014e-308" 0010000000000000 / OK   "2.2250738585072011e-308" 000FFFFFFFFFFFFF / OK
+ *   "0.1000000000000000055511151231257827" 3FB999999999999A / OK   "123456789012345678901234567890" 45F8EE90FF6C373E / OK
+ *   "9007199254740993.0000000000000000" 4340000000000000 / OK   "9007199254740993.0000000000000001" 4340000000000000 / HARD
+ *   "0e99999" 0000000000000000 / OK   "1e" + 59 zeros + "5" (62 bytes) 40F86A0000000000 / OK
+ *   "1e" + 61 zeros + "5" (64 bytes) 40F86A0000000000 / OK
+ *   63 zeros + "1" (64 bytes) 3FF0000000000000 / OK   the same with one more zero (65 bytes) 0000000000000000 / LONG
+ *   "1e" 0000000000000000 / BAD   "e5" 0000000000000000 / BAD   "." 0000000000000000 / BAD   "1.2.3" 0000000000000000 / BAD
+ *   "+.e1" 0000000000000000 / BAD   "0x10" 0000000000000000 / BAD   "1e+" 0000000000000000 / BAD
+ *   "nan" without BRX_PARSE_WORDS 0000000000000000 / BAD   "-Infinity" with BRX_PARSE_WORDS FFF0000000000000 / OK
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued (behind an
+ * index call on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.  No scratch, no
+ * upload, no read back, one launch: calls on different HIP streams may overlap without limit.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits; BRX_TAKE_TRIM_CR without
+ * BRX_TAKE_NO_DELIM; delim_len 0 or above 16; only one of sel_stream / sel_rec; val or status NULL; then m = 0 returns BRX_SUCCESS, no
+ * launch; then out_off, len, count or pos_off NULL; pos NULL with n_pos > 0; all-records mode with n = 0; span out of range (and m
+ * beyond what one launch addresses).
+ * Not in scope: a slow path for HARD on the device (big-integer comparison per lane: the named follow-up); float32 output; hex float,
+ * thousands separators, decimal commas; records above 64 bytes.
+ * Reads the tables of the selected entries, every byte of their records of at most 64 bytes once and 16 or 32 bytes of a 10.4 KB
+ * table of powers of five per number, writes 9 m; one launch; no reference counterpart. */
+#define BRX_PARSE_WORDS 64u /* brx_parse_f64_batch only: [+-]? nan / inf / infinity in any letter case are values, not BAD */
+#define BRX_PARSE_HARD   6u /* brx_parse_f64_batch only: more than 19 digits and too close to call; val or its successor is the answer */
+int brx_parse_f64_batch(brx_ctx *ctx,
+                        const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                        const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos,
+                        uint32_t delim_len, uint32_t flags,
+                        const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                        uint8_t quote,
+                        double *val, uint8_t *status,
+                        void *hip_stream);
 
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
