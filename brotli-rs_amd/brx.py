@@ -38,6 +38,11 @@ PARSE_MAX_LEN = 64  # BRX_PARSE_MAX_LEN
 PARSE_MAX_SCALE = 18  # BRX_PARSE_MAX_SCALE
 PARSE_WORDS = 64  # BRX_PARSE_WORDS (brx_parse_f64_batch only)
 PARSE_HARD = 6  # BRX_PARSE_HARD (brx_parse_f64_batch only: val or the next double away from zero)
+TIME_DATE, TIME_TIME, TIME_STAMP = 0, 1, 2  # BRX_TIME_DATE / _TIME / _STAMP (brx_parse_time_batch)
+TIME_KINDS = {"date": TIME_DATE, "time": TIME_TIME, "stamp": TIME_STAMP}
+TIME_UNITS = {"s": 0, "ms": 3, "us": 6, "ns": 9}  # unit -> scale
+TIME_MAX_SCALE = 9  # BRX_TIME_MAX_SCALE
+TIME_NO_ZONE = -32768  # BRX_TIME_NO_ZONE
 
 
 class BrxError(RuntimeError):
@@ -130,6 +135,11 @@ def load_library():
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p]
+    L.brx_parse_time_batch.restype = ctypes.c_int
+    L.brx_parse_time_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -187,7 +197,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
                     "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch",
-                    "brx_parse_batch"]
+                    "brx_parse_batch", "brx_parse_time_batch"]
 # Exported names with a digit in them.  They are kept apart because tests/test_abi.py compares EXPORTED_SYMBOLS with the names it reads
 # from include/brx.h by the pattern brx_[a-z_]+, which such a name does not match; tests/test_parse_f64_abi.py holds this list to the
 # header and to the library.
@@ -703,6 +713,76 @@ class Context:
                                 sel_rec.data_ptr() if sel_rec is not None else None, m, PARSE_KINDS[kind], int(scale),
                                 bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
         return val_buf[:m], status_buf[:m]
+
+    def parse_time_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
+                                sel_stream_ptr, sel_rec_ptr, m, kind, scale, quote, val_ptr, status_ptr, zone_ptr=None, hip_stream=None):
+        """brx_parse_time_batch on raw device pointers: val[j] (int64) = the day number (TIME_DATE) or the count of 10**-scale s (TIME_TIME,
+        TIME_STAMP) that entry j of the selection spells, status[j] (uint8) = PARSE_OK .. PARSE_LONG, zone[j] (int16, zone_ptr may be None) =
+        the offset in minutes east of UTC or TIME_NO_ZONE; the selection, the positions and the TAKE_* flags exactly as for
+        take_batch_device, PARSE_SPACES / PARSE_QUOTED in the same flags word; scale 0 .. 9 (0 with TIME_DATE), quote a byte value."""
+        rc = self._lib.brx_parse_time_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len,
+                                            flags, sel_stream_ptr, sel_rec_ptr, m, kind, scale, quote, val_ptr, status_ptr, zone_ptr, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_parse_time_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def parse_time_batch(self, out, out_off, out_len, count, pos_off, pos, sel_stream=None, sel_rec=None, delim_len=1, keep_delim=False,
+                         trim_cr=False, spaces=False, quote=None, kind="stamp", unit="s", zones=False, stream=None):
+        """Every selected record of the decoded streams of a batch as a date, a time of day or a timestamp, parsed on the device.  Every
+        argument up to trim_cr as for parse_batch (keep_delim defaults to False: a stamp never contains its delimiter).  kind: "date"
+        (YYYY-MM-DD: val = days since 1970-01-01, unit must be "s" or 0), "time" (HH:MM[:SS[.fff]]: val = units since midnight) or "stamp"
+        (a date, then optionally T, t or a blank, a time and a zone Z / +HH:MM / +HHMM / +HH: val = units since 1970-01-01T00:00:00Z; a
+        stamp without a zone is read as UTC, a date alone is midnight).  unit: "s", "ms", "us", "ns", or an integer scale 0 .. 9 (units
+        of 10**-scale s); fraction digits beyond the unit are cut off toward minus infinity.  A comma is accepted as the decimal mark.
+        spaces=True drops leading and trailing blanks and tabs; quote=b'"' then drops one enclosing pair of that byte.
+        Returns (val, status), or (val, status, zone) with zones=True: torch.int64 / torch.uint8 / torch.int16 device tensors.  status[j]
+        is one of PARSE_OK, PARSE_INEXACT (a non-zero fraction digit was cut off), PARSE_EMPTY (nothing there), PARSE_RANGE (outside 64
+        bits, only at scales 8 and 9: val is the nearest bound), PARSE_BAD (not such a stamp, or a field out of its range) and
+        PARSE_LONG (a record above 64 bytes, not looked at); val is 0 for EMPTY, BAD and LONG.  zone[j] is the offset in minutes east
+        of UTC where the status is OK or INEXACT and the text carried a zone, else TIME_NO_ZONE.  Nothing is read back.  With unit="ns",
+        val.cpu().numpy().view("datetime64[ns]") matches numpy.datetime64[ns] (with "date", view("datetime64[D]")).  The stamps of a log
+        batch:
+            count, _, pos_off, pos, _ = ctx.index_set_batch(out, out_off, out_len, delims=b",\n", no_quote=True, no_escape=True)
+            val, status, zone = ctx.parse_time_batch(out, out_off, out_len, count, pos_off, pos, trim_cr=True, unit="ms", zones=True)"""
+        import torch
+        if trim_cr and keep_delim:
+            raise BrxError("parse_time_batch: trim_cr needs keep_delim=False")
+        if kind not in TIME_KINDS:
+            raise BrxError("parse_time_batch: kind is one of %s" % ", ".join(sorted(TIME_KINDS)))
+        if isinstance(unit, str):
+            if unit not in TIME_UNITS:
+                raise BrxError("parse_time_batch: unit is one of %s, or a scale 0 .. 9" % ", ".join(sorted(TIME_UNITS)))
+            scale = TIME_UNITS[unit]
+        else:
+            scale = int(unit)
+            if not 0 <= scale <= TIME_MAX_SCALE:
+                raise BrxError("parse_time_batch: unit is one of %s, or a scale 0 .. 9" % ", ".join(sorted(TIME_UNITS)))
+        if quote is not None and len(bytes(quote)) != 1:
+            raise BrxError("parse_time_batch: quote is one byte, or None")
+        n = int(out_len.numel())
+        if (sel_stream is None) != (sel_rec is None):
+            raise BrxError("parse_time_batch: sel_stream and sel_rec go together")
+        hs = stream.cuda_stream if stream is not None else None
+        flags = ((0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
+                 | (PARSE_QUOTED if quote is not None else 0))
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if sel_stream is not None:
+                sel_stream = sel_stream.to(torch.int32).contiguous()
+                sel_rec = sel_rec.to(torch.int64).contiguous()
+                m = int(sel_stream.numel())
+            else:
+                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
+            val_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
+            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
+            zone_buf = torch.empty(max(m, 1), dtype=torch.int16, device=out.device) if zones else None
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        self.parse_time_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
+                                     pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
+                                     sel_stream.data_ptr() if sel_stream is not None else None,
+                                     sel_rec.data_ptr() if sel_rec is not None else None, m, TIME_KINDS[kind], scale,
+                                     bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(),
+                                     zone_buf.data_ptr() if zones else None, hip_stream=hs)
+        return (val_buf[:m], status_buf[:m], zone_buf[:m]) if zones else (val_buf[:m], status_buf[:m])
 
     def parse_f64_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                                sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream=None):

@@ -37,6 +37,7 @@
 #include "brx_hash.h"
 #include "brx_parse.h"
 #include "brx_parse_f64.h"
+#include "brx_parse_time.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -1707,6 +1708,48 @@ extern "C" int brx_parse_f64_batch(brx_ctx *c, const uint8_t *out, const uint64_
         HIP_TRY(hipSetDevice(c->device));
         st = hip_stream ? (hipStream_t)hip_stream : c->stream;
         brx_launch_parse_f64(a, quote, (uint64_t *)val, status, st); // (the kernel writes bit patterns: no double arithmetic on the device)
+        HIP_TRY(hipGetLastError());
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- selected records of the decoded streams of a batch as dates, times and timestamps (brx_parse_time.hip) ------------------
+extern "C" int brx_parse_time_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                                    const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                                    uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint32_t kind, uint32_t scale,
+                                    uint8_t quote, int64_t *val, uint8_t *status, int16_t *zone, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: ctx is NULL");
+    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | BRX_PARSE_SPACES | BRX_PARSE_QUOTED))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: unknown flag bits");
+    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
+    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: delim_len is not 1 .. 16");
+    if ((sel_stream == nullptr) != (sel_rec == nullptr))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: sel_stream and sel_rec go together");
+    if (kind > BRX_TIME_STAMP) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: kind is not BRX_TIME_DATE, _TIME or _STAMP");
+    if (scale > BRX_TIME_MAX_SCALE || (scale && kind == BRX_TIME_DATE))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: scale is not 0 .. 9, or not 0 with BRX_TIME_DATE");
+    if (!val || !status) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: val or status is NULL");
+    if (m == 0) return BRX_SUCCESS;
+    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: NULL table");
+    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: pos is NULL with n_pos > 0");
+    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: all-records mode with n = 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: span out of range");
+    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: m out of range"); // the grid follows from m alone
+    BrxTakeArgs a;
+    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
+    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
+    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the parse its own two)
+    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        brx_launch_parse_time(a, kind, scale, quote, val, status, zone, st);
         HIP_TRY(hipGetLastError());
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));

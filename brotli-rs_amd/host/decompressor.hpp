@@ -261,5 +261,18 @@ inline void parse_f64_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *ou
                             status, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_parse_f64_batch: ") + brx_last_error());
 }
+// Every selected record as a date, a time of day or a timestamp (the selection, the positions and the BRX_TAKE_* flags as for take_batch;
+// BRX_PARSE_SPACES / BRX_PARSE_QUOTED in the same flags word): kind BRX_TIME_DATE (val[j] = days since 1970-01-01), BRX_TIME_TIME or
+// BRX_TIME_STAMP (val[j] = units of 10^-scale s, scale 0 .. 9, rounded toward minus infinity), status[j] (BRX_PARSE_OK, _INEXACT, _EMPTY,
+// _RANGE, _BAD, _LONG) and, if zone is given, zone[j] = the offset in minutes east of UTC or BRX_TIME_NO_ZONE.  ISO 8601 / RFC 3339 in
+// the extended format only; records above 64 bytes are LONG.
+inline void parse_time_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                             const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                             uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint32_t kind, uint32_t scale,
+                             uint8_t quote, int64_t *val, uint8_t *status, int16_t *zone = nullptr, void *stream = nullptr) {
+    if (brx_parse_time_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m, kind, scale,
+                             quote, val, status, zone, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_parse_time_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

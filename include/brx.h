@@ -654,7 +654,7 @@ int brx_hash_batch(brx_ctx *ctx,
  * BRX_PARSE_INT / BRX_PARSE_HEX; val or status NULL; then m = 0 returns BRX_SUCCESS, no launch; then out_off, len, count or pos_off
  * NULL; pos NULL with n_pos > 0; all-records mode with n = 0; span out of range (and m beyond what one launch addresses).
  * Not in scope: binary floating point (a correctly rounded double needs a power-of-ten table and a slow path: the named follow-up;
- * BRX_PARSE_DEC with a scale is the exact substitute); exponents, thousands separators, locale decimal commas; dates and times;
+ * BRX_PARSE_DEC with a scale is the exact substitute); exponents, thousands separators, locale decimal commas; dates and times (brx_parse_time_batch below);
  * unescaping; records above 64 bytes.  (The follow-up is brx_parse_f64_batch below: doubles, with exponents, as a call of its own.)
  * Reads the tables of the selected entries and every byte of their records of at most 64 bytes once, writes 9 m; one launch; no
  * reference counterpart. */
@@ -751,6 +751,99 @@ int brx_parse_f64_batch(brx_ctx *ctx,
                         uint8_t quote,
                         double *val, uint8_t *status,
                         void *hip_stream);
+
+/* ---- every selected record of the decoded bytes of a batch as a date, a time of day or a timestamp (device memory only) --------
+ * The column type that brx_parse_batch and brx_parse_f64_batch both call BAD: "2024-03-10T07:08:09.123+05:30".  val[j] is the day
+ * number or the instant that entry j of a selection spells, status[j] says whether it spelled one, zone[j] which offset it carried,
+ * straight from the arena -- no bytes gathered, nothing read back, exact integer arithmetic that a CPU reproduces bit for bit.
+ * Every argument up to m means word for word what it means for brx_take_batch / brx_hash_batch / brx_parse_batch: the arena (out,
+ * out_off, len, n, span), the positions (count, pos_off, pos, n_pos), delim_len, THE RULE with all its clamps, the flags
+ * BRX_TAKE_NO_DELIM / BRX_TAKE_TRIM_CR (BRX_TAKE_TRIM_CR only with BRX_TAKE_NO_DELIM), pairs mode and all-records mode.  An entry that
+ * selects nothing is the empty record.  All pointers are DEVICE memory.  val and status (m entries each) are both required; zone (m
+ * entries) may be NULL.  Nothing at or beyond out + span, or in front of out, is ever loaded.
+ * Two more bits of the same flags word: BRX_PARSE_SPACES, BRX_PARSE_QUOTED (BRX_PARSE_WORDS and every other bit are refused).  kind:
+ * BRX_TIME_DATE, BRX_TIME_TIME, BRX_TIME_STAMP.  scale: 0 .. BRX_TIME_MAX_SCALE = 9 for BRX_TIME_TIME and BRX_TIME_STAMP (0 seconds, 3
+ * milliseconds, 6 microseconds, 9 nanoseconds), 0 for BRX_TIME_DATE.  status[j] is one of BRX_PARSE_OK, _INEXACT, _EMPTY, _RANGE, _BAD,
+ * _LONG: there is no new status value.
+ * THE PARSE, TIME, for the record r[0 .. L) that the rule gives (after BRX_TAKE_TRIM_CR):
+ *   1. L > BRX_PARSE_MAX_LEN = 64: LONG, val = 0.  None of the record's bytes is loaded (beyond the one BRX_TAKE_TRIM_CR looks at).
+ *   2. With BRX_PARSE_SPACES: leading and trailing bytes 0x20 and 0x09 are dropped.
+ *   3. With BRX_PARSE_QUOTED: if at least 2 bytes remain and the first and the last both equal `quote`, both are dropped -- once.
+ *      Without the flag `quote` is ignored.
+ *   4. What remains is t[0 .. T).  T = 0: EMPTY, val = 0.
+ *   5. Grammar, matched against all of t, D = 0-9:
+ *        date = DDDD '-' DD '-' DD                      (the year has exactly four digits, 0000 .. 9999)
+ *        time = DD ':' DD ( ':' DD ( [.,] D+ )? )?
+ *        zone = [Zz] | [+-] DD ':' DD | [+-] DDDD | [+-] DD
+ *        DATE: date        TIME: time        STAMP: date ( [Tt ] time zone? )?
+ *      A date alone is midnight.  A comma is accepted as the decimal mark because Python's logging default prints one.  A mismatch:
+ *      BAD, val = 0.
+ *   6. Field ranges; a violation is BAD.  Month 01 .. 12.  Day 01 .. the month's length in the proleptic Gregorian calendar: year y is
+ *      leap iff y % 4 == 0 and (y % 100 != 0 or y % 400 == 0); year 0000 is leap.  Hour 00 .. 23, minute 00 .. 59, second 00 .. 59.
+ *      Zone hours 00 .. 23, zone minutes 00 .. 59.  There is no 24:00 and no second 60.
+ *   7. Value.  days = days from 1970-01-01 to the date, 0 for TIME.  off = the zone's offset in seconds east of UTC, 0 for Z, for no
+ *      zone and for -00:00.  secs = days * 86400 + hh * 3600 + mm * 60 + ss - off.  With F the fraction digits (none: empty):
+ *      V = secs * 10^scale + (the first `scale` digits of F, padded with '0' up to `scale` digits, read as an integer): the instant in
+ *      units of 10^-scale s, rounded toward minus infinity.  DATE: scale must be 0 and V = days.
+ *      V > 2^63 - 1: RANGE, val = INT64_MAX.  V < -2^63: RANGE, val = INT64_MIN.  Otherwise val = V, and the status is INEXACT if a
+ *      digit of F behind the first `scale` is not '0', else OK.  RANGE wins over INEXACT.  Only scales 8 and 9 can reach RANGE within
+ *      years 0000 .. 9999.
+ *   8. zone[j], if given: the offset in minutes east of UTC, -1439 .. 1439, when the status is OK or INEXACT and the text carried a
+ *      zone (Z is 0); BRX_TIME_NO_ZONE in every other case: no zone in the text, DATE, TIME, and every other status.  The caller can
+ *      tell naive stamps from aware ones and can rebuild the wall-clock time.
+ * Check values, val / status, MAX = 9223372036854775807, MIN = -9223372036854775808:
+ *   DATE:  "1970-01-01" 0 / OK   "1969-12-31" -1 / OK   "0000-01-01" -719528 / OK   "0000-02-29" -719469 / OK
+ *         "2000-02-29" 11016 / OK   "9999-12-31" 2932896 / OK   "1900-02-29" 0 / BAD   "2100-02-29" 0 / BAD   "2024-02-30" 0 / BAD
+ *         "2023-04-31" 0 / BAD   "2023-00-10" 0 / BAD   "2023-13-01" 0 / BAD   "2023-01-00" 0 / BAD   "2023-1-01" 0 / BAD
+ *         "20230101" 0 / BAD   "+2023-01-01" 0 / BAD   "2023-01-01T00:00" 0 / BAD   "" 0 / EMPTY
+ *   TIME, scale 0:  "00:00" 0 / OK   "23:59:59" 86399 / OK   "24:00:00" 0 / BAD   "12:60" 0 / BAD   "23:59:60" 0 / BAD
+ *         "12:34:56." 0 / BAD   "12:34.5" 0 / BAD   "12:34:56Z" 0 / BAD   "1:02:03" 0 / BAD
+ *   TIME, scale 3:  "12:34:56.789" 45296789 / OK   "12:34:56,7891" 45296789 / INEXACT
+ *   TIME, scale 9:  "23:59:59.999999999" 86399999999999 / OK
+ *   STAMP, scale 0:  "1970-01-01T00:00:00Z" 0 / OK   "2024-03-10" 1710028800 / OK   "2024-03-10 07:08" 1710054480 / OK
+ *         "2024-03-10T07:08Z" 1710054480 / OK   "2024-03-10t07:08:09z" 1710054489 / OK
+ *         "2024-03-10T07:08:09-0800" 1710083289 / OK, zone -480   "2024-03-10T07:08:09+01" 1710050889 / OK, zone 60
+ *         "2024-03-10T07:08:09-00:00" 1710054489 / OK, zone 0   "1969-12-31T23:59:59.5Z" -1 / INEXACT
+ *         "0000-01-01T00:00:00+23:59" -62167305540 / OK   "9999-12-31T23:59:59-23:59" 253402387139 / OK
+ *         "2024-03-10T07:08:09+24:00" 0 / BAD   "2024-03-10T07:08:09+05:60" 0 / BAD   "2024-03-10T07:08:09+5" 0 / BAD
+ *         "2024-03-10T07:08:09+05:3" 0 / BAD   "2024-03-10T07:08:09 Z" 0 / BAD   "2024-03-10T07:08:60Z" 0 / BAD
+ *         "2024-03-10T24:00:00Z" 0 / BAD   "2024-03-10T07:08:09.Z" 0 / BAD   "2024-03-10T07Z" 0 / BAD   "2024-03-10T" 0 / BAD
+ *         "2024-02-30T00:00:00Z" 0 / BAD   "2024-03-10_07:08:09" 0 / BAD   "2024-03-10T07:08:09ZZ" 0 / BAD
+ *   STAMP, scale 3:  "2024-03-10 07:08:09,123" 1710054489123 / OK, zone BRX_TIME_NO_ZONE   "2024-03-10T07:08:09.1239" 1710054489123 / INEXACT
+ *         "1969-12-31T23:59:59.5Z" -500 / OK   "2024-03-10T07:08:09." + 38 zeros + "+05:30" (64 bytes) 1710034689000 / OK
+ *         the same with 39 zeros (65 bytes) 0 / LONG   "2024-03-10T07:08:09.123" + 40 zeros + "1" (64 bytes) 1710054489123 / INEXACT
+ *   STAMP, scale 6:  "2024-03-10T07:08:09.5+05:30" 1710034689500000 / OK, zone 330
+ *   STAMP, scale 9:  "2262-04-11T23:47:16.854775807Z" MAX / OK   "2262-04-11T23:47:16.854775808Z" MAX / RANGE
+ *         "2262-04-11T23:47:16.8547758079Z" MAX / INEXACT   "1677-09-21T00:12:43.145224192Z" MIN / OK
+ *         "1677-09-21T00:12:43.145224191Z" MIN / RANGE   "1677-09-21T00:12:43.1452241919Z" MIN / RANGE
+ *         "9999-12-31T23:59:59Z" MAX / RANGE   "0000-01-01T00:00:00Z" MIN / RANGE
+ *   STAMP, scale 0, with BRX_PARSE_SPACES | BRX_PARSE_QUOTED, quote '"' (the text between the brackets):
+ *         [ "2024-03-10T07:08:09Z"\t] 1710054489 / OK   [" 2024-03-10"] 0 / BAD   [""] 0 / EMPTY
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued (behind an
+ * index call on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.  No scratch, no
+ * upload, no read back, one launch: calls on different HIP streams may overlap without limit.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits (64 is one of them);
+ * BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM; delim_len 0 or above 16; only one of sel_stream / sel_rec; kind above 2; scale above 9, or
+ * non-zero with BRX_TIME_DATE; val or status NULL; then m = 0 returns BRX_SUCCESS, no launch; then out_off, len, count or pos_off
+ * NULL; pos NULL with n_pos > 0; all-records mode with n = 0; span out of range (and m beyond what one launch addresses).
+ * Not in scope: the basic format without separators, week dates and ordinal dates; years outside 0000 .. 9999, expanded or signed
+ * years; month names (RFC 2822, Common Log Format); 12-hour clocks; zone names and DST rules; leap seconds and 24:00; durations and
+ * intervals; records above 64 bytes.
+ * Reads the tables of the selected entries and every byte of their records of at most 64 bytes once, writes 9 m (11 m with zone); one
+ * launch; no reference counterpart. */
+#define BRX_TIME_DATE  0u /* DDDD-DD-DD: val = days since 1970-01-01 */
+#define BRX_TIME_TIME  1u /* DD:DD[:DD[.D+]]: val = units of 10^-scale s since midnight */
+#define BRX_TIME_STAMP 2u /* date, then optionally a time and a zone: val = units of 10^-scale s since 1970-01-01T00:00:00Z */
+#define BRX_TIME_MAX_SCALE 9u
+#define BRX_TIME_NO_ZONE (-32768) /* zone[j] where no offset is reported */
+int brx_parse_time_batch(brx_ctx *ctx,
+                         const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                         const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos,
+                         uint32_t delim_len, uint32_t flags,
+                         const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                         uint32_t kind, uint32_t scale, uint8_t quote,
+                         int64_t *val, uint8_t *status, int16_t *zone,
+                         void *hip_stream);
 
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
