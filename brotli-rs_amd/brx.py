@@ -43,6 +43,9 @@ TIME_KINDS = {"date": TIME_DATE, "time": TIME_TIME, "stamp": TIME_STAMP}
 TIME_UNITS = {"s": 0, "ms": 3, "us": 6, "ns": 9}  # unit -> scale
 TIME_MAX_SCALE = 9  # BRX_TIME_MAX_SCALE
 TIME_NO_ZONE = -32768  # BRX_TIME_NO_ZONE
+TEXT_CSV, TEXT_JSON, TEXT_BACKSLASH = 0, 1, 2  # BRX_TEXT_CSV / _JSON / _BACKSLASH (brx_unescape_batch)
+TEXT_DIALECTS = {"csv": TEXT_CSV, "json": TEXT_JSON, "backslash": TEXT_BACKSLASH}
+TEXT_OK, TEXT_BARE, TEXT_NULL, TEXT_BAD = 0, 1, 2, 3  # BRX_TEXT_OK ... (the status byte)
 
 
 class BrxError(RuntimeError):
@@ -140,6 +143,11 @@ def load_library():
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.brx_unescape_batch.restype = ctypes.c_int
+    L.brx_unescape_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -197,7 +205,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
                     "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch",
-                    "brx_parse_batch", "brx_parse_time_batch"]
+                    "brx_parse_batch", "brx_parse_time_batch", "brx_unescape_batch"]
 # Exported names with a digit in them.  They are kept apart because tests/test_abi.py compares EXPORTED_SYMBOLS with the names it reads
 # from include/brx.h by the pattern brx_[a-z_]+, which such a name does not match; tests/test_parse_f64_abi.py holds this list to the
 # header and to the library.
@@ -783,6 +791,87 @@ class Context:
                                      bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(),
                                      zone_buf.data_ptr() if zones else None, hip_stream=hs)
         return (val_buf[:m], status_buf[:m], zone_buf[:m]) if zones else (val_buf[:m], status_buf[:m])
+
+    def unescape_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
+                              sel_stream_ptr, sel_rec_ptr, m, dialect, quote, escape, text_len_ptr, status_ptr, dst_off_ptr=None,
+                              dst_ptr=None, total=0, hip_stream=None):
+        """brx_unescape_batch on raw device pointers: the string that entry j of the selection spells under `dialect` (TEXT_CSV, TEXT_JSON,
+        TEXT_BACKSLASH; quote and escape are byte values); the selection, the positions and the TAKE_* flags exactly as for
+        take_batch_device, PARSE_SPACES in the same flags word.  Size mode (dst_off_ptr and dst_ptr None): text_len[j] (uint64) = the
+        text's length, status[j] (uint8) = TEXT_OK, TEXT_BARE, TEXT_NULL or TEXT_BAD.  Fill mode: dst[dst_off[j] + t] = the text's byte t
+        for t below its length and its room; nothing at or beyond `total` is written; text_len_ptr and status_ptr may be None."""
+        rc = self._lib.brx_unescape_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len,
+                                          flags, sel_stream_ptr, sel_rec_ptr, m, dialect, quote, escape, text_len_ptr, status_ptr,
+                                          dst_off_ptr, dst_ptr, total, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_unescape_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def unescape_batch(self, out, out_off, out_len, count, pos_off, pos, sel_stream=None, sel_rec=None, delim_len=1, keep_delim=False,
+                       trim_cr=True, dialect="json", quote=0x22, escape=0x5C, spaces=False, stride=None, stream=None):
+        """Every selected record of the decoded streams of a batch as the string it spells, unquoted and unescaped on the device.  Every
+        argument up to trim_cr as for take_batch -- except that keep_delim defaults to False and trim_cr to True (with keep_delim=True
+        trim_cr must be False).  dialect: "csv" (RFC 4180: an enclosing pair of `quote`, "" inside it is one quote), "json" (a JSON
+        string: \\n \\" \\/ \\uXXXX and surrogate pairs come out as UTF-8; anything not quoted -- null, a number, true -- comes out as
+        it stands, TEXT_BARE) or "backslash" (PostgreSQL COPY text, MySQL tab dumps: \\t \\n \\\\ ..., \\N alone is TEXT_NULL).  quote and
+        escape are byte values; spaces=True drops leading and trailing blanks and tabs first.
+        Returns (dst, dst_off, text_len, status): uint8, int64, int64 and uint8 device tensors; status[j] is TEXT_OK, TEXT_BARE,
+        TEXT_NULL or TEXT_BAD (malformed somewhere: the text is what the walk emitted, see include/brx.h).  stride=None: the texts back
+        to back, dst_off the exclusive prefix sum of text_len (a size-mode call, a cumsum on the device, one scalar read back for the
+        total, a fill-mode call).  stride=S: one call, text j in dst[j * S .. (j + 1) * S), cut at S (at the byte: text_len[j] > S
+        tells), the rest of its row zero; nothing is read back.  The "text" values of a JSON Lines batch, rows {"id": 7, "text": "..."}:
+            count, _, pos_off, pos, what = ctx.index_set_batch(out, out_off, out_len, delims=b'{}[]:,\\n')
+            # the records are the pieces between two structural bytes: per row "", the key "id", 7, the key "text", the value, ""
+            streams = torch.repeat_interleave(torch.arange(count.numel(), device=out.device), count + 1)
+            rec = torch.arange(streams.numel(), device=out.device) - (pos_off + torch.arange(count.numel(), device=out.device))[streams]
+            pick = rec % 6 == 4
+            dst, dst_off, text_len, status = ctx.unescape_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=streams[pick],
+                                                                sel_rec=rec[pick], dialect="json", spaces=True)"""
+        import torch
+        if trim_cr and keep_delim:
+            raise BrxError("unescape_batch: trim_cr needs keep_delim=False")
+        if dialect not in TEXT_DIALECTS:
+            raise BrxError("unescape_batch: dialect is one of %s" % ", ".join(sorted(TEXT_DIALECTS)))
+        n = int(out_len.numel())
+        if (sel_stream is None) != (sel_rec is None):
+            raise BrxError("unescape_batch: sel_stream and sel_rec go together")
+        hs = stream.cuda_stream if stream is not None else None
+        flags = (0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if sel_stream is not None:
+                sel_stream = sel_stream.to(torch.int32).contiguous()
+                sel_rec = sel_rec.to(torch.int64).contiguous()
+                m = int(sel_stream.numel())
+            else:
+                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
+            len_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
+            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
+            text_len = len_buf[:m]
+            if stride is not None:
+                dst_off = torch.arange(m, dtype=torch.int64, device=out.device) * int(stride)
+                total = m * int(stride)
+                dst = torch.zeros(max(total, 1), dtype=torch.uint8, device=out.device)
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
+        args = (out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(), pos_off.data_ptr(),
+                pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
+                sel_stream.data_ptr() if sel_stream is not None else None, sel_rec.data_ptr() if sel_rec is not None else None, m,
+                TEXT_DIALECTS[dialect], int(quote), int(escape))
+        if stride is not None:
+            if m:
+                self.unescape_batch_device(*args, len_buf.data_ptr(), status_buf.data_ptr(), dst_off.data_ptr(), dst.data_ptr(), total,
+                                           hip_stream=hs)
+            return dst[:total], dst_off, text_len, status_buf[:m]
+        self.unescape_batch_device(*args, len_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ends = torch.cumsum(text_len, 0)
+            dst_off = ends - text_len
+            total = int(ends[-1].item()) if m else 0  # (the read-back: waits for the size pass)
+            dst = torch.empty(max(total, 1), dtype=torch.uint8, device=out.device)
+        if stream is None:
+            torch.cuda.current_stream(out.device).synchronize()
+        if m:
+            self.unescape_batch_device(*args, None, None, dst_off.data_ptr(), dst.data_ptr(), total, hip_stream=hs)
+        return dst[:total], dst_off, text_len, status_buf[:m]
 
     def parse_f64_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                                sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream=None):

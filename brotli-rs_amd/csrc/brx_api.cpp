@@ -38,6 +38,7 @@
 #include "brx_parse.h"
 #include "brx_parse_f64.h"
 #include "brx_parse_time.h"
+#include "brx_unescape.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -1750,6 +1751,55 @@ extern "C" int brx_parse_time_batch(brx_ctx *c, const uint8_t *out, const uint64
         HIP_TRY(hipSetDevice(c->device));
         st = hip_stream ? (hipStream_t)hip_stream : c->stream;
         brx_launch_parse_time(a, kind, scale, quote, val, status, zone, st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- selected records of the decoded streams of a batch as the strings they spell (brx_unescape.hip) -------------------------
+extern "C" int brx_unescape_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                                  const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                                  uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint32_t dialect,
+                                  uint32_t quote, uint32_t escape, uint64_t *text_len, uint8_t *status, const uint64_t *dst_off, uint8_t *dst,
+                                  uint64_t total, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: ctx is NULL");
+    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | BRX_PARSE_SPACES))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: unknown flag bits");
+    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
+    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: delim_len is not 1 .. 16");
+    if ((sel_stream == nullptr) != (sel_rec == nullptr))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: sel_stream and sel_rec go together");
+    if (dialect > BRX_TEXT_BACKSLASH) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: dialect is not BRX_TEXT_CSV, _JSON or _BACKSLASH");
+    if (quote > 255u || escape > 255u) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: quote or escape is not a byte value");
+    if (dialect == BRX_TEXT_JSON && quote == escape) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: BRX_TEXT_JSON with quote == escape");
+    if ((dst_off == nullptr) != (dst == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: dst_off and dst go together");
+    if (!dst && (!text_len || !status)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: text_len or status is NULL in size mode");
+    if (m == 0) return BRX_SUCCESS;
+    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: NULL table");
+    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: pos is NULL with n_pos > 0");
+    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: all-records mode with n = 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: span out of range");
+    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: m out of range"); // the grid follows from m alone
+    if (dst && (total > (uint64_t)1 << 62 || brx_take_chunks(total, dst) > 0x7fffffffull))
+        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: total out of range (more than 8 TiB)");
+    BrxTakeArgs a;
+    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
+    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
+    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the text its own one)
+    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    BrxTextArgs x;
+    x.dialect = dialect; x.q = quote; x.e = escape;
+    x.text_len = text_len; x.status = status; x.dst_off = dst_off; x.dst = dst; x.total = total;
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        brx_launch_unescape(a, x, st);
         HIP_TRY(hipGetLastError());
     }
     if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));

@@ -274,5 +274,19 @@ inline void parse_time_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *o
                              quote, val, status, zone, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_parse_time_batch: ") + brx_last_error());
 }
+// Every selected record as the string it spells (the selection, the positions and the BRX_TAKE_* flags as for take_batch; BRX_PARSE_SPACES
+// in the same flags word): dialect BRX_TEXT_CSV (an enclosing pair of `quote`, two of them inside it are one), BRX_TEXT_JSON (string
+// escapes, \uXXXX and surrogate pairs as UTF-8) or BRX_TEXT_BACKSLASH (COPY text; `escape` 'N' alone is BRX_TEXT_NULL).  Size mode
+// (dst_off, dst nullptr): text_len[j] and status[j] (BRX_TEXT_OK, _BARE, _NULL, _BAD).  Fill mode: the text at dst[dst_off[j] ..], cut
+// at the entry's room; text_len and status may then be nullptr.  A text is never longer than its record.
+inline void unescape_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                           const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                           uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint32_t dialect, uint32_t quote,
+                           uint32_t escape, uint64_t *text_len, uint8_t *status, const uint64_t *dst_off = nullptr, uint8_t *dst = nullptr,
+                           uint64_t total = 0, void *stream = nullptr) {
+    if (brx_unescape_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m, dialect, quote,
+                           escape, text_len, status, dst_off, dst, total, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_unescape_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

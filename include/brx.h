@@ -845,6 +845,83 @@ int brx_parse_time_batch(brx_ctx *ctx,
                          int64_t *val, uint8_t *status, int16_t *zone,
                          void *hip_stream);
 
+/* ---- selected records of the decoded bytes of a batch as the strings they spell (device memory only) -----------
+ * The column type that is left: strings.  brx_take_batch copies a record's bytes as they stand, so the "text": "..." of a JSON Lines
+ * row still carries its \n, \" and \uXXXX, and a CSV field its "" -- this call resolves them on the device: u_j is the string that
+ * entry j of a selection spells, status[j] says how it was written, straight from the arena into a destination.
+ * Every argument up to m means word for word what it means for brx_take_batch / brx_hash_batch / brx_parse_batch: the arena (out,
+ * out_off, len, n, span), the positions (count, pos_off, pos, n_pos), delim_len, THE RULE with all its clamps, the flags
+ * BRX_TAKE_NO_DELIM / BRX_TAKE_TRIM_CR (BRX_TAKE_TRIM_CR only with BRX_TAKE_NO_DELIM), pairs mode and all-records mode.  An entry that
+ * selects nothing is the empty record.  All pointers are DEVICE memory.  One more bit of the same flags word: BRX_PARSE_SPACES; every
+ * other bit is refused.  dialect: BRX_TEXT_CSV, BRX_TEXT_JSON, BRX_TEXT_BACKSLASH; quote and escape are byte values (q, e below).
+ * dst_off, dst, total and the ROOM of an entry are exactly those of brx_take_batch's fill mode.  Nothing at or beyond out + span, or
+ * in front of out, is ever loaded; in fact no byte outside an entry's record is: the look-ahead of an escape ends at the record's end,
+ * whatever follows it in the arena is never loaded.
+ * SIZE MODE (dst_off == NULL and dst == NULL; text_len and status required): text_len[j] = L'_j, the length of u_j, and status[j].
+ * FILL MODE (dst_off and dst both given; text_len and status may each be NULL, and if given they are written as in size mode):
+ *   dst[dst_off[j] + t] = u_j[t]     for t < min(L'_j, room_j)
+ * A room's bytes behind its text are left as they were, and no byte at index >= total is written.  A text cut by its room is cut at
+ * the byte: that may be inside a UTF-8 sequence (the caller sees it from text_len[j] > room_j).
+ * L' <= T <= L holds in every case, so a caller may size the rooms from brx_take_batch's rec_len (or use one stride that holds the
+ * longest record) without a size-mode call.
+ * THE TEXT, for the record r[0 .. L) that the rule gives (after BRX_TAKE_TRIM_CR).  With BRX_PARSE_SPACES leading and trailing bytes
+ * 0x20 and 0x09 are dropped first; what remains is t[0 .. T).  Every output is defined, also for malformed input: BAD means
+ * "malformed somewhere; the text is what the walk below emitted".
+ *   BRX_TEXT_CSV (RFC 4180; e is ignored).  T = 0 or t[0] != q: BARE, u = t (so an unquoted empty field and "" are told apart).
+ *     t[0] = q and (T < 2 or t[T-1] != q): BAD, u = t.  Otherwise walk the body t[1 .. T-1) from the left: a q followed by a q inside
+ *     the body emits one q and skips both; a q otherwise emits q and sets BAD; any other byte is emitted.  OK unless BAD was set.
+ *   BRX_TEXT_JSON (q != e required).  T = 0 or t[0] != q: BARE, u = t (null, numbers and true come out this way).  Otherwise walk from
+ *     i = 1.  At e that is the last byte of t: emit e, BAD, advance 1.  At e with c = t[i+1]: c is q, e or '/': emit c, advance 2;
+ *     c is b f n r t: emit 08 0C 0A 0D 09, advance 2; c is u and t[i+2 .. i+6) lies inside t and is four hex digits of either case,
+ *     a code unit cu: not a surrogate: emit its UTF-8 (1 to 3 bytes; \u0000 emits one zero byte), advance 6; cu in D800..DBFF and
+ *     t[i+6 .. i+12) lies inside t and is e, u and four hex digits of a code unit in DC00..DFFF: emit the 4 UTF-8 bytes of the
+ *     pair, advance 12; any other surrogate: emit EF BF BD, BAD, advance 6.  Anything else (unknown letter, short or non-hex \u): emit
+ *     e, BAD, advance 1.  At q: if i = T-1 it is the closing quote and the walk ends, otherwise emit q, BAD, advance 1.  Any other byte
+ *     is emitted: raw control bytes and the UTF-8 of the raw bytes pass unchecked.  A walk that reaches T without the closing quote
+ *     sets BAD.  The tests on c are made in this order (it matters only for odd choices of q and e).
+ *   BRX_TEXT_BACKSLASH (PostgreSQL COPY text, MySQL tab dumps; q is ignored, no quoting).  t is exactly e 'N': NULL, L' = 0.
+ *     Otherwise walk from 0: e as the last byte: emit e, BAD; e followed by b f n r t v 0: emit 08 0C 0A 0D 09 0B 00; e followed by
+ *     any other byte c: emit c (e itself, a delimiter, a quote); any other byte is emitted.  Never BARE.
+ * Check values, q = '"', e = '\', record and text between brackets, text bytes in hex where they are not printable:
+ *   JSON:  ["a\tb"] 61 09 62 / OK   ["\u00e9"] C3 A9 / OK   ["\ud83d\ude00"] F0 9F 98 80 / OK   ["\\"] 5C / OK   [""] empty / OK
+ *          [null] [null] / BARE   ["\ud83d"] EF BF BD / BAD   ["\ud83d\u0041"] EF BF BD 41 / BAD   ["\ude00x"] EF BF BD 78 / BAD
+ *          ["\u12"] [\u12] / BAD   ["\x"] [\x] / BAD   ["a"b"] [a"b] / BAD   ["abc\"] [abc"] / BAD   ["abc] [abc] / BAD
+ *          ["] empty / BAD
+ *   JSON with BRX_PARSE_SPACES:  [ "x"<09>] [x] / OK
+ *   CSV:   ["a""b"] [a"b] / OK   [""""] ["] / OK   [""] empty / OK   [] empty / BARE   [abc] [abc] / BARE   ["""] ["] / BAD
+ *          ["a"b"] [a"b] / BAD   ["abc] ["abc] / BAD   ["] ["] / BAD
+ *   BACKSLASH:  [a\tb] 61 09 62 / OK   [\,] [,] / OK   [\\N] [\N] / OK   [x\N] [xN] / OK   [\N] empty / NULL   [a\] [a\] / BAD
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued (behind an
+ * index call on the same stream it needs no synchronisation in between).  The context's lock is held to enqueue only.  No scratch, no
+ * upload, no read back, one launch: calls on different HIP streams may overlap without limit.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; unknown flag bits; BRX_TAKE_TRIM_CR without
+ * BRX_TAKE_NO_DELIM; delim_len 0 or above 16; only one of sel_stream / sel_rec; dialect above 2; quote or escape above 255;
+ * BRX_TEXT_JSON with quote == escape; only one of dst_off / dst; text_len or status NULL in size mode; then m = 0 returns BRX_SUCCESS,
+ * no launch; then out_off, len, count or pos_off NULL; pos NULL with n_pos > 0; all-records mode with n = 0; span out of range (and m
+ * or total beyond what one launch addresses).
+ * Not in scope: octal and \x escapes; validation of UTF-8 or of raw control bytes; JSON values other than strings (no nested
+ * parsing); escapes that act only inside quotes; re-quoting; padding values other than "left as it was".
+ * Reads the tables of the selected entries and the bytes of their records, writes the texts and 9 m; one launch; no reference
+ * counterpart.  Two cases are computed by one lane per record, whatever its length, while the other lanes of its wavefront wait:
+ * BRX_TEXT_JSON with an escape byte that is a hex digit, and, with BRX_PARSE_SPACES, the blanks around a record, which are dropped
+ * byte by byte before anything else (a record of some KiB of blanks costs its wavefront a serial walk of that length). */
+#define BRX_TEXT_CSV       0u
+#define BRX_TEXT_JSON      1u
+#define BRX_TEXT_BACKSLASH 2u
+#define BRX_TEXT_OK   0u /* quoted (CSV, JSON) or plain (BACKSLASH), and well-formed */
+#define BRX_TEXT_BARE 1u /* CSV, JSON: not quoted; the text is the record (after BRX_PARSE_SPACES) */
+#define BRX_TEXT_NULL 2u /* BACKSLASH: the record is e 'N'; the text is empty */
+#define BRX_TEXT_BAD  3u /* malformed somewhere; the text is what the walk emitted */
+int brx_unescape_batch(brx_ctx *ctx,
+                       const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                       const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos,
+                       uint32_t delim_len, uint32_t flags,
+                       const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                       uint32_t dialect, uint32_t quote, uint32_t escape,
+                       uint64_t *text_len, uint8_t *status,
+                       const uint64_t *dst_off, uint8_t *dst, uint64_t total,
+                       void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one
