@@ -4,6 +4,7 @@ item, `brotli::Decompressor<R: Read>` (reference src/lib.rs:377-410, 2173-2193).
 Plumbing only: every decode goes through the C ABI into the gfx950 kernels.  If the library or a GPU is
 missing this module FAILS LOUDLY (BrxError); there is no CPU fallback anywhere in the product path.
 """
+import collections
 import contextlib
 import ctypes
 import io
@@ -118,36 +119,14 @@ def load_library():
     L.brx_find_batch.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                  ctypes.c_void_p]
-    L.brx_take_batch.restype = ctypes.c_int
-    L.brx_take_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                 ctypes.c_uint64, ctypes.c_void_p]
-    L.brx_hash_batch.restype = ctypes.c_int
-    L.brx_hash_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                 ctypes.c_void_p]
-    L.brx_parse_batch.restype = ctypes.c_int
-    L.brx_parse_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.brx_parse_f64_batch.restype = ctypes.c_int
-    L.brx_parse_f64_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p]
-    L.brx_parse_time_batch.restype = ctypes.c_int
-    L.brx_parse_time_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.brx_unescape_batch.restype = ctypes.c_int
-    L.brx_unescape_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    # the record calls: ctx, then out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m
+    P, U32, U64, U8 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint8
+    rec = [P, P, P, P, U32, U64, P, P, P, U64, U32, U32, P, P, U64]
+    for name, own in (("brx_take_batch", [P, P, P, U64, P]), ("brx_hash_batch", [U64, P, P, P]), ("brx_parse_batch", [U32, U32, U8, P, P, P]),
+                      ("brx_parse_f64_batch", [U8, P, P, P]), ("brx_parse_time_batch", [U32, U32, U8, P, P, P, P]),
+                      ("brx_unescape_batch", [U32, U32, U32, P, P, P, P, U64, P])):
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name).argtypes = rec + own
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -220,6 +199,77 @@ def status_str(code: int) -> str:
 OPTIONS = {"command_loop": 1, "loop_build": 2, "queue_order": 3, "hand_up": 4, "levels": 5, "tiny_bytes": 6,
            "host_in_place": 7, "grid_cap": 8, "small_bytes": 9, "small_waves": 10, "trace": 11, "reader_window": 12, "level4": 13, "reader_mb_room": 14,
            "reader_batch": 15}
+
+
+def _on(stream):
+    """The torch stream that a call's own torch work goes to: `stream`, or the current one."""
+    import torch
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+# ---- what the wrappers of the record calls share (take, hash, parse, parse_f64, parse_time, unescape: DESIGN.md 17.1) ----------------
+# A wrapper raises in this order: _rec_flags (trim_cr), its own checks, _rec_begin (the pairing); `who` is the method's name.
+def _rec_flags(who, keep_delim, trim_cr, own=0):
+    """The flags word: take's two bits from keep_delim / trim_cr, and the call's own."""
+    if trim_cr and keep_delim:
+        raise BrxError("%s: trim_cr needs keep_delim=False" % who)
+    return (0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | own
+
+
+_Rec = collections.namedtuple("_Rec", "head m hs sel_stream sel_rec bufs")
+
+
+def _rec_begin(who, out, out_off, out_len, count, pos_off, pos, sel_stream, sel_rec, delim_len, flags, stream, dtypes):
+    """The selection as the device call takes it: a _Rec of the 14 leading arguments of the *_batch_device method (`head`), the number
+    of entries (`m`), the hip stream (`hs`), the converted selection tensors (`sel_stream`, `sel_rec`: `head` holds their addresses,
+    so the wrapper keeps the _Rec until its last device call) and one uninitialised tensor of max(m, 1) elements (an empty view has no
+    address) per name in `dtypes` (None for None), allocated on `stream` (`bufs`)."""
+    import torch
+    n = int(out_len.numel())
+    if (sel_stream is None) != (sel_rec is None):
+        raise BrxError("%s: sel_stream and sel_rec go together" % who)
+    with _on(stream):
+        if sel_stream is not None:
+            sel_stream = sel_stream.to(torch.int32).contiguous()
+            sel_rec = sel_rec.to(torch.int64).contiguous()
+            m = int(sel_stream.numel())
+        else:
+            m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
+        bufs = [None if t is None else torch.empty(max(m, 1), dtype=getattr(torch, t), device=out.device) for t in dtypes]
+    head = (out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(), pos_off.data_ptr(),
+            pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
+            sel_stream.data_ptr() if sel_stream is not None else None, sel_rec.data_ptr() if sel_rec is not None else None, m)
+    return _Rec(head, m, stream.cuda_stream if stream is not None else None, sel_stream, sel_rec, bufs)
+
+
+def _rec_sync(out, stream):
+    """In front of a device call that follows torch work: without `stream` the call runs on the context's stream, which is not ordered
+    behind torch's."""
+    import torch
+    if stream is None:
+        torch.cuda.current_stream(out.device).synchronize()
+
+
+def _rec_gather(out, stream, m, length, stride, fill_pass):
+    """The destination of m records and its filling.  stride=None: the records back to back, dst_off the exclusive prefix sum of
+    `length`, which a size pass has been launched to write (one scalar is read back for the total).  stride=S: rows of S bytes, zero
+    behind a record's end; `length` is not read and nothing is read back.  Then fill_pass(dst_off_ptr, dst_ptr, total), unless m is 0.
+    Returns (dst, dst_off)."""
+    import torch
+    with _on(stream):
+        if stride is None:
+            ends = torch.cumsum(length, 0)
+            dst_off = ends - length
+            total = int(ends[-1].item()) if m else 0  # (the read-back: waits for the size pass)
+            dst = torch.empty(max(total, 1), dtype=torch.uint8, device=out.device)
+        else:
+            dst_off = torch.arange(m, dtype=torch.int64, device=out.device) * int(stride)
+            total = m * int(stride)
+            dst = torch.zeros(max(total, 1), dtype=torch.uint8, device=out.device)
+    _rec_sync(out, stream)
+    if m:
+        fill_pass(dst_off.data_ptr(), dst.data_ptr(), total)
+    return dst[:total], dst_off
 
 
 class Context:
@@ -579,44 +629,14 @@ class Context:
         delimiter, trim_cr=True (only then) also one CR in front of it.  Returns (dst, dst_off, rec_len): uint8 and two int64 device
         tensors.  stride=None: the records back to back, dst_off the exclusive prefix sum of rec_len (one scalar is read back for the
         total).  stride=S: record j in dst[j * S .. (j + 1) * S), cut at S, the rest of its row zero; nothing is read back."""
-        import torch
-        if trim_cr and keep_delim:
-            raise BrxError("take_batch: trim_cr needs keep_delim=False")
-        n = int(out_len.numel())
-        if (sel_stream is None) != (sel_rec is None):
-            raise BrxError("take_batch: sel_stream and sel_rec go together")
-        hs = stream.cuda_stream if stream is not None else None
-        flags = (0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            if sel_stream is not None:
-                sel_stream = sel_stream.to(torch.int32).contiguous()
-                sel_rec = sel_rec.to(torch.int64).contiguous()
-                m = int(sel_stream.numel())
-            else:
-                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
-            rec_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
-            rec_len = rec_buf[:m]
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        args = (out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(), pos_off.data_ptr(),
-                pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
-                sel_stream.data_ptr() if sel_stream is not None else None, sel_rec.data_ptr() if sel_rec is not None else None, m)
-        self.take_batch_device(*args, rec_buf.data_ptr(), hip_stream=hs)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            if stride is None:
-                ends = torch.cumsum(rec_len, 0)
-                dst_off = ends - rec_len
-                total = int(ends[-1].item()) if m else 0  # (the read-back: waits for the size pass)
-                dst = torch.empty(max(total, 1), dtype=torch.uint8, device=out.device)
-            else:
-                dst_off = torch.arange(m, dtype=torch.int64, device=out.device) * int(stride)
-                total = m * int(stride)
-                dst = torch.zeros(max(total, 1), dtype=torch.uint8, device=out.device)
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()
-        if m:
-            self.take_batch_device(*args, None, dst_off.data_ptr(), dst.data_ptr(), total, hip_stream=hs)
-        return dst[:total], dst_off, rec_len
+        flags = _rec_flags("take_batch", keep_delim, trim_cr)
+        r = _rec_begin("take_batch", out, out_off, out_len, count, pos_off, pos, sel_stream, sel_rec, delim_len, flags, stream, ("int64",))
+        rec_len = r.bufs[0][:r.m]
+        _rec_sync(out, stream)
+        self.take_batch_device(*r.head, r.bufs[0].data_ptr(), hip_stream=r.hs)
+        dst, dst_off = _rec_gather(out, stream, r.m, rec_len, stride,
+                                   lambda off, dst, total: self.take_batch_device(*r.head, None, off, dst, total, hip_stream=r.hs))
+        return dst, dst_off, rec_len
 
     def hash_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                           sel_stream_ptr, sel_rec_ptr, m, seed, hash_ptr, rec_len_ptr=None, hip_stream=None):
@@ -642,31 +662,13 @@ class Context:
             dst, dst_off, rec_len = ctx.take_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=stream_of, sel_rec=rec_of,
                                                    keep_delim=False, trim_cr=True)
         (entry j of all-records mode is record j - (pos_off[i] + i) of stream i).  key % G shards the records over G workers."""
-        import torch
-        if trim_cr and keep_delim:
-            raise BrxError("hash_batch: trim_cr needs keep_delim=False")
-        n = int(out_len.numel())
-        if (sel_stream is None) != (sel_rec is None):
-            raise BrxError("hash_batch: sel_stream and sel_rec go together")
-        hs = stream.cuda_stream if stream is not None else None
-        flags = (0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            if sel_stream is not None:
-                sel_stream = sel_stream.to(torch.int32).contiguous()
-                sel_rec = sel_rec.to(torch.int64).contiguous()
-                m = int(sel_stream.numel())
-            else:
-                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
-            hash_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
-            len_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device) if want_len else None
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        self.hash_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
-                               pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
-                               sel_stream.data_ptr() if sel_stream is not None else None,
-                               sel_rec.data_ptr() if sel_rec is not None else None, m, seed, hash_buf.data_ptr(),
-                               len_buf.data_ptr() if want_len else None, hip_stream=hs)
-        return (hash_buf[:m], len_buf[:m]) if want_len else hash_buf[:m]
+        flags = _rec_flags("hash_batch", keep_delim, trim_cr)
+        r = _rec_begin("hash_batch", out, out_off, out_len, count, pos_off, pos, sel_stream, sel_rec, delim_len, flags, stream,
+                       ("int64", "int64" if want_len else None))
+        hash_buf, len_buf = r.bufs
+        _rec_sync(out, stream)
+        self.hash_batch_device(*r.head, seed, hash_buf.data_ptr(), len_buf.data_ptr() if want_len else None, hip_stream=r.hs)
+        return (hash_buf[:r.m], len_buf[:r.m]) if want_len else hash_buf[:r.m]
 
     def parse_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                            sel_stream_ptr, sel_rec_ptr, m, kind, scale, quote, val_ptr, status_ptr, hip_stream=None):
@@ -691,36 +693,18 @@ class Context:
         not looked at); val is 0 for EMPTY, BAD and LONG.  Nothing is read back.  The prices of a CSV batch, in cents:
             count, _, pos_off, pos, _ = ctx.index_set_batch(out, out_off, out_len, delims=b",\n", no_quote=True, no_escape=True)
             val, status = ctx.parse_batch(out, out_off, out_len, count, pos_off, pos, trim_cr=True, kind="dec", scale=2)"""
-        import torch
-        if trim_cr and keep_delim:
-            raise BrxError("parse_batch: trim_cr needs keep_delim=False")
+        flags = _rec_flags("parse_batch", keep_delim, trim_cr, (PARSE_SPACES if spaces else 0) | (PARSE_QUOTED if quote is not None else 0))
         if kind not in PARSE_KINDS:
             raise BrxError("parse_batch: kind is one of %s" % ", ".join(sorted(PARSE_KINDS)))
         if quote is not None and len(bytes(quote)) != 1:
             raise BrxError("parse_batch: quote is one byte, or None")
-        n = int(out_len.numel())
-        if (sel_stream is None) != (sel_rec is None):
-            raise BrxError("parse_batch: sel_stream and sel_rec go together")
-        hs = stream.cuda_stream if stream is not None else None
-        flags = ((0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
-                 | (PARSE_QUOTED if quote is not None else 0))
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            if sel_stream is not None:
-                sel_stream = sel_stream.to(torch.int32).contiguous()
-                sel_rec = sel_rec.to(torch.int64).contiguous()
-                m = int(sel_stream.numel())
-            else:
-                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
-            val_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
-            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        self.parse_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
-                                pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
-                                sel_stream.data_ptr() if sel_stream is not None else None,
-                                sel_rec.data_ptr() if sel_rec is not None else None, m, PARSE_KINDS[kind], int(scale),
-                                bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
-        return val_buf[:m], status_buf[:m]
+        r = _rec_begin("parse_batch", out, out_off, out_len, count, pos_off, pos, sel_stream, sel_rec, delim_len, flags, stream,
+                       ("int64", "uint8"))
+        val_buf, status_buf = r.bufs
+        _rec_sync(out, stream)
+        self.parse_batch_device(*r.head, PARSE_KINDS[kind], int(scale), bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(),
+                                status_buf.data_ptr(), hip_stream=r.hs)
+        return val_buf[:r.m], status_buf[:r.m]
 
     def parse_time_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                                 sel_stream_ptr, sel_rec_ptr, m, kind, scale, quote, val_ptr, status_ptr, zone_ptr=None, hip_stream=None):
@@ -751,9 +735,7 @@ class Context:
         batch:
             count, _, pos_off, pos, _ = ctx.index_set_batch(out, out_off, out_len, delims=b",\n", no_quote=True, no_escape=True)
             val, status, zone = ctx.parse_time_batch(out, out_off, out_len, count, pos_off, pos, trim_cr=True, unit="ms", zones=True)"""
-        import torch
-        if trim_cr and keep_delim:
-            raise BrxError("parse_time_batch: trim_cr needs keep_delim=False")
+        flags = _rec_flags("parse_time_batch", keep_delim, trim_cr, (PARSE_SPACES if spaces else 0) | (PARSE_QUOTED if quote is not None else 0))
         if kind not in TIME_KINDS:
             raise BrxError("parse_time_batch: kind is one of %s" % ", ".join(sorted(TIME_KINDS)))
         if isinstance(unit, str):
@@ -766,31 +748,13 @@ class Context:
                 raise BrxError("parse_time_batch: unit is one of %s, or a scale 0 .. 9" % ", ".join(sorted(TIME_UNITS)))
         if quote is not None and len(bytes(quote)) != 1:
             raise BrxError("parse_time_batch: quote is one byte, or None")
-        n = int(out_len.numel())
-        if (sel_stream is None) != (sel_rec is None):
-            raise BrxError("parse_time_batch: sel_stream and sel_rec go together")
-        hs = stream.cuda_stream if stream is not None else None
-        flags = ((0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
-                 | (PARSE_QUOTED if quote is not None else 0))
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            if sel_stream is not None:
-                sel_stream = sel_stream.to(torch.int32).contiguous()
-                sel_rec = sel_rec.to(torch.int64).contiguous()
-                m = int(sel_stream.numel())
-            else:
-                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
-            val_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
-            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
-            zone_buf = torch.empty(max(m, 1), dtype=torch.int16, device=out.device) if zones else None
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        self.parse_time_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
-                                     pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
-                                     sel_stream.data_ptr() if sel_stream is not None else None,
-                                     sel_rec.data_ptr() if sel_rec is not None else None, m, TIME_KINDS[kind], scale,
-                                     bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(),
-                                     zone_buf.data_ptr() if zones else None, hip_stream=hs)
-        return (val_buf[:m], status_buf[:m], zone_buf[:m]) if zones else (val_buf[:m], status_buf[:m])
+        r = _rec_begin("parse_time_batch", out, out_off, out_len, count, pos_off, pos, sel_stream, sel_rec, delim_len, flags, stream,
+                       ("int64", "uint8", "int16" if zones else None))
+        val_buf, status_buf, zone_buf = r.bufs
+        _rec_sync(out, stream)
+        self.parse_time_batch_device(*r.head, TIME_KINDS[kind], scale, bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(),
+                                     status_buf.data_ptr(), zone_buf.data_ptr() if zones else None, hip_stream=r.hs)
+        return (val_buf[:r.m], status_buf[:r.m], zone_buf[:r.m]) if zones else (val_buf[:r.m], status_buf[:r.m])
 
     def unescape_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                               sel_stream_ptr, sel_rec_ptr, m, dialect, quote, escape, text_len_ptr, status_ptr, dst_off_ptr=None,
@@ -826,52 +790,21 @@ class Context:
             pick = rec % 6 == 4
             dst, dst_off, text_len, status = ctx.unescape_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=streams[pick],
                                                                 sel_rec=rec[pick], dialect="json", spaces=True)"""
-        import torch
-        if trim_cr and keep_delim:
-            raise BrxError("unescape_batch: trim_cr needs keep_delim=False")
+        flags = _rec_flags("unescape_batch", keep_delim, trim_cr, PARSE_SPACES if spaces else 0)
         if dialect not in TEXT_DIALECTS:
             raise BrxError("unescape_batch: dialect is one of %s" % ", ".join(sorted(TEXT_DIALECTS)))
-        n = int(out_len.numel())
-        if (sel_stream is None) != (sel_rec is None):
-            raise BrxError("unescape_batch: sel_stream and sel_rec go together")
-        hs = stream.cuda_stream if stream is not None else None
-        flags = (0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            if sel_stream is not None:
-                sel_stream = sel_stream.to(torch.int32).contiguous()
-                sel_rec = sel_rec.to(torch.int64).contiguous()
-                m = int(sel_stream.numel())
-            else:
-                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
-            len_buf = torch.empty(max(m, 1), dtype=torch.int64, device=out.device)  # (an empty view has no address)
-            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
-            text_len = len_buf[:m]
-            if stride is not None:
-                dst_off = torch.arange(m, dtype=torch.int64, device=out.device) * int(stride)
-                total = m * int(stride)
-                dst = torch.zeros(max(total, 1), dtype=torch.uint8, device=out.device)
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        args = (out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(), pos_off.data_ptr(),
-                pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
-                sel_stream.data_ptr() if sel_stream is not None else None, sel_rec.data_ptr() if sel_rec is not None else None, m,
-                TEXT_DIALECTS[dialect], int(quote), int(escape))
-        if stride is not None:
-            if m:
-                self.unescape_batch_device(*args, len_buf.data_ptr(), status_buf.data_ptr(), dst_off.data_ptr(), dst.data_ptr(), total,
-                                           hip_stream=hs)
-            return dst[:total], dst_off, text_len, status_buf[:m]
-        self.unescape_batch_device(*args, len_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            ends = torch.cumsum(text_len, 0)
-            dst_off = ends - text_len
-            total = int(ends[-1].item()) if m else 0  # (the read-back: waits for the size pass)
-            dst = torch.empty(max(total, 1), dtype=torch.uint8, device=out.device)
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()
-        if m:
-            self.unescape_batch_device(*args, None, None, dst_off.data_ptr(), dst.data_ptr(), total, hip_stream=hs)
-        return dst[:total], dst_off, text_len, status_buf[:m]
+        r = _rec_begin("unescape_batch", out, out_off, out_len, count, pos_off, pos, sel_stream, sel_rec, delim_len, flags, stream,
+                       ("int64", "uint8"))
+        len_buf, status_buf = r.bufs
+        head = r.head + (TEXT_DIALECTS[dialect], int(quote), int(escape))
+        sizes = (len_buf.data_ptr(), status_buf.data_ptr())
+        if stride is None:  # (with rows of `stride` the one call below is both passes)
+            _rec_sync(out, stream)
+            self.unescape_batch_device(*head, *sizes, hip_stream=r.hs)
+            sizes = (None, None)
+        dst, dst_off = _rec_gather(out, stream, r.m, len_buf[:r.m], stride,
+                                   lambda off, dst, total: self.unescape_batch_device(*head, *sizes, off, dst, total, hip_stream=r.hs))
+        return dst, dst_off, len_buf[:r.m], status_buf[:r.m]
 
     def parse_f64_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                                sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream=None):
@@ -902,32 +835,17 @@ class Context:
             count, _, pos_off, pos, _ = ctx.index_set_batch(out, out_off, out_len, delims=b",\\n", no_quote=True, no_escape=True)
             val, status = ctx.parse_f64_batch(out, out_off, out_len, count, pos_off, pos, trim_cr=True, finish=True)"""
         import torch
-        if trim_cr and keep_delim:
-            raise BrxError("parse_f64_batch: trim_cr needs keep_delim=False")
+        flags = _rec_flags("parse_f64_batch", keep_delim, trim_cr, (PARSE_SPACES if spaces else 0) | (PARSE_QUOTED if quote is not None else 0)
+                           | (PARSE_WORDS if words else 0))
         if quote is not None and len(bytes(quote)) != 1:
             raise BrxError("parse_f64_batch: quote is one byte, or None")
         n = int(out_len.numel())
-        if (sel_stream is None) != (sel_rec is None):
-            raise BrxError("parse_f64_batch: sel_stream and sel_rec go together")
-        hs = stream.cuda_stream if stream is not None else None
-        flags = ((0 if keep_delim else TAKE_NO_DELIM) | (TAKE_TRIM_CR if trim_cr else 0) | (PARSE_SPACES if spaces else 0)
-                 | (PARSE_QUOTED if quote is not None else 0) | (PARSE_WORDS if words else 0))
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            if sel_stream is not None:
-                sel_stream = sel_stream.to(torch.int32).contiguous()
-                sel_rec = sel_rec.to(torch.int64).contiguous()
-                m = int(sel_stream.numel())
-            else:
-                m = int(pos.numel()) + n  # sum(count) + n for a consistent caller; no read back
-            val_buf = torch.empty(max(m, 1), dtype=torch.float64, device=out.device)  # (an empty view has no address)
-            status_buf = torch.empty(max(m, 1), dtype=torch.uint8, device=out.device)
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        self.parse_f64_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
-                                    pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, int(pos.numel()), int(delim_len), flags,
-                                    sel_stream.data_ptr() if sel_stream is not None else None,
-                                    sel_rec.data_ptr() if sel_rec is not None else None, m,
-                                    bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(), hip_stream=hs)
+        r = _rec_begin("parse_f64_batch", out, out_off, out_len, count, pos_off, pos, sel_stream, sel_rec, delim_len, flags, stream,
+                       ("float64", "uint8"))
+        m, sel_stream, sel_rec, (val_buf, status_buf) = r.m, r.sel_stream, r.sel_rec, r.bufs
+        _rec_sync(out, stream)
+        self.parse_f64_batch_device(*r.head, bytes(quote)[0] if quote is not None else 0, val_buf.data_ptr(), status_buf.data_ptr(),
+                                    hip_stream=r.hs)
         val, status = val_buf[:m], status_buf[:m]
         if not finish or m == 0:
             return val, status

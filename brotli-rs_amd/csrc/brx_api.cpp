@@ -1300,6 +1300,49 @@ extern "C" int brx_compact_batch(brx_ctx *c, const uint8_t *out, const uint64_t 
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
+// ---- what the launches of the calls below share -----------------------------------------------------------------------------
+// `body(stream)` under the context's lock, on the context's device: the stream is the caller's, or the context's own, which is then
+// synchronised behind the lock.
+template <class F>
+static int run_locked(brx_ctx *c, void *hip_stream, F body) {
+    hipStream_t st;
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIP_TRY(hipSetDevice(c->device));
+        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+        const int rc = body(st);
+        if (rc != BRX_SUCCESS) return rc;
+    }
+    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
+    return BRX_SUCCESS;
+}
+
+static int launched() { // behind a launch: what it left
+    HIP_TRY(hipGetLastError());
+    return BRX_SUCCESS;
+}
+
+// One launch of a tile pass on `st`, under the lock: a region of `bytes` of the ring (regions of `grow` bytes where
+// it has to grow), `launch(scratch)`, the region's event behind it.
+template <class F>
+static int ring_launch(PassRing &ring, size_t bytes, size_t grow, const char *oom, hipStream_t st, F launch) {
+    int rc = ring_reserve(ring, bytes, grow, oom);
+    void *scratch = nullptr;
+    if (rc == BRX_SUCCESS) rc = ring_take(ring, &scratch);
+    if (rc != BRX_SUCCESS) return rc;
+    launch(scratch);
+    if ((rc = launched()) != BRX_SUCCESS) return rc;
+    return ring_record(ring, st);
+}
+
+// ... as a whole call: `launch(scratch, stream)`
+template <class F>
+static int run_pass(brx_ctx *c, void *hip_stream, PassRing &ring, size_t bytes, size_t grow, const char *oom, F launch) {
+    return run_locked(c, hip_stream, [&](hipStream_t st) {
+        return ring_launch(ring, bytes, grow, oom, st, [&](void *scratch) { launch(scratch, st); });
+    });
+}
+
 // ---- CRC-32 / CRC-32C of the decoded streams of a batch (brx_digest.hip) ---------------------------------------------------
 extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
                                 uint32_t *digest, const uint32_t *expect, uint32_t *mismatch, void *hip_stream) {
@@ -1311,11 +1354,7 @@ extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, c
     if (n == 0) return BRX_SUCCESS;
     if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_digest_batch: NULL table");
     const uint32_t poly = kind == BRX_DIGEST_CRC32 ? 0xEDB88320u : 0x82F63B78u;
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    return run_locked(c, hip_stream, [&](hipStream_t st) {
         uint32_t *&tab = c->d_digest_tab[kind - 1u];
         if (!tab) { // first use of this kind on this context: tables from the polynomial, by the host
             std::vector<uint32_t> h(BRX_DG_WORDS);
@@ -1330,18 +1369,12 @@ extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, c
             }
             tab = d;
         }
-        int rc = ring_reserve(c->digest_ring, brx_dg_region_bytes(n), brx_dg_region_bytes((size_t)n + n / 4u + 1024u),
-                              "digest scratch allocation failed");
-        void *scratch = nullptr;
-        if (rc == BRX_SUCCESS) rc = ring_take(c->digest_ring, &scratch);
-        if (rc != BRX_SUCCESS) return rc;
         // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU, 80 of its 160 KiB of LDS (max_grid = 16 per CU)
-        brx_launch_digest(out, out_off, len, n, tab, poly, scratch, digest, expect, mismatch, c->max_grid / 4u, st);
-        HIP_TRY(hipGetLastError());
-        if ((rc = ring_record(c->digest_ring, st)) != BRX_SUCCESS) return rc;
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+        return ring_launch(c->digest_ring, brx_dg_region_bytes(n), brx_dg_region_bytes((size_t)n + n / 4u + 1024u),
+                           "digest scratch allocation failed", st, [&](void *scratch) {
+                               brx_launch_digest(out, out_off, len, n, tab, poly, scratch, digest, expect, mismatch, c->max_grid / 4u, st);
+                           });
+    });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1358,24 +1391,12 @@ extern "C" int brx_index_batch(brx_ctx *c, uint8_t delim, const uint8_t *out, co
     // what the scratch of a launch must hold follows from n and span alone: no length is read back
     const uint64_t max_tiles = brx_ix_max_tiles(n, span);
     if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: span out of range");
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        int rc = ring_reserve(c->index_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
-                              brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                              "index scratch allocation failed");
-        void *scratch = nullptr;
-        if (rc == BRX_SUCCESS) rc = ring_take(c->index_ring, &scratch);
-        if (rc != BRX_SUCCESS) return rc;
-        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    return run_pass(c, hip_stream, c->index_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
+                    brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                    "index scratch allocation failed", [&](void *scratch, hipStream_t st) {
         brx_launch_index(out, out_off, len, n, span, delim, scratch, max_tiles, count, pos_off, pos, total, c->max_grid / 4u, st);
-        HIP_TRY(hipGetLastError());
-        if ((rc = ring_record(c->index_ring, st)) != BRX_SUCCESS) return rc;
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1394,25 +1415,13 @@ extern "C" int brx_index_quoted_batch(brx_ctx *c, uint8_t delim, uint8_t quote, 
     // what the scratch of a launch must hold follows from n and span alone: no length is read back
     const uint64_t max_tiles = brx_ix_max_tiles(n, span);
     if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_quoted_batch: span out of range");
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        int rc = ring_reserve(c->index_quoted_ring, brx_iq_region_bytes(n, (size_t)max_tiles),
-                              brx_iq_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                              "quoted index scratch allocation failed");
-        void *scratch = nullptr;
-        if (rc == BRX_SUCCESS) rc = ring_take(c->index_quoted_ring, &scratch);
-        if (rc != BRX_SUCCESS) return rc;
-        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    return run_pass(c, hip_stream, c->index_quoted_ring, brx_iq_region_bytes(n, (size_t)max_tiles),
+                    brx_iq_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                    "quoted index scratch allocation failed", [&](void *scratch, hipStream_t st) {
         brx_launch_index_quoted(out, out_off, len, n, span, delim, quote, scratch, max_tiles, count, open, pos_off, pos, total,
                                 c->max_grid / 4u, st);
-        HIP_TRY(hipGetLastError());
-        if ((rc = ring_record(c->index_quoted_ring, st)) != BRX_SUCCESS) return rc;
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1436,25 +1445,13 @@ extern "C" int brx_index_escaped_batch(brx_ctx *c, uint8_t delim, uint8_t quote,
     // what the scratch of a launch must hold follows from n and span alone: no length is read back
     const uint64_t max_tiles = brx_ix_max_tiles(n, span);
     if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: span out of range");
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        int rc = ring_reserve(c->index_escaped_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
-                              brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                              "escaped index scratch allocation failed");
-        void *scratch = nullptr;
-        if (rc == BRX_SUCCESS) rc = ring_take(c->index_escaped_ring, &scratch);
-        if (rc != BRX_SUCCESS) return rc;
-        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    return run_pass(c, hip_stream, c->index_escaped_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
+                    brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                    "escaped index scratch allocation failed", [&](void *scratch, hipStream_t st) {
         brx_launch_index_escaped(out, out_off, len, n, span, delim, quote, escape, flags, scratch, max_tiles, count, open, pos_off, pos,
                                  total, c->max_grid / 4u, st);
-        HIP_TRY(hipGetLastError());
-        if ((rc = ring_record(c->index_escaped_ring, st)) != BRX_SUCCESS) return rc;
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1492,25 +1489,13 @@ extern "C" int brx_index_set_batch(brx_ctx *c, const uint8_t *delims, uint32_t n
     // what the scratch of a launch must hold follows from n and span alone: no length is read back
     const uint64_t max_tiles = brx_ix_max_tiles(n, span);
     if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: span out of range");
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        int rc = ring_reserve(c->index_set_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
-                              brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                              "set index scratch allocation failed");
-        void *scratch = nullptr;
-        if (rc == BRX_SUCCESS) rc = ring_take(c->index_set_ring, &scratch);
-        if (rc != BRX_SUCCESS) return rc;
-        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    return run_pass(c, hip_stream, c->index_set_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
+                    brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                    "set index scratch allocation failed", [&](void *scratch, hipStream_t st) {
         brx_launch_index_set(out, out_off, len, n, span, set, n_delims, quote, escape, flags, scratch, max_tiles, count, open, pos_off,
                              pos, what, total, c->max_grid / 4u, st);
-        HIP_TRY(hipGetLastError());
-        if ((rc = ring_record(c->index_set_ring, st)) != BRX_SUCCESS) return rc;
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1530,27 +1515,58 @@ extern "C" int brx_find_batch(brx_ctx *c, const uint8_t *needle, uint32_t needle
     // what the scratch of a launch must hold follows from n and span alone: no length is read back
     const uint64_t max_tiles = brx_ix_max_tiles(n, span);
     if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: span out of range");
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        int rc = ring_reserve(c->find_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
-                              brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                              "find scratch allocation failed");
-        void *scratch = nullptr;
-        if (rc == BRX_SUCCESS) rc = ring_take(c->find_ring, &scratch);
-        if (rc != BRX_SUCCESS) return rc;
-        // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU).  The needle's bytes are read here, into
-        // the launch arguments: the caller may reuse its buffer when the call returns.
+    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU).  The needle's bytes are read here, into
+    // the launch arguments: the caller may reuse its buffer when the call returns.
+    return run_pass(c, hip_stream, c->find_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
+                    brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
+                    "find scratch allocation failed", [&](void *scratch, hipStream_t st) {
         brx_launch_find(out, out_off, len, n, span, needle, needle_len, scratch, max_tiles, count, pos_off, pos, total, c->max_grid / 4u,
                         st);
-        HIP_TRY(hipGetLastError());
-        if ((rc = ring_record(c->find_ring, st)) != BRX_SUCCESS) return rc;
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- the record calls: entry j of a selection, under the positions of an index pass, with take's flags -----
+// What the six calls below share is defined once, here; a call states its name, its own flag bits, its own checks and its launch.
+static int refuse(const char *call, const char *what) { // "<call>: <what>", as brx_last_error() gives it
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", call, what);
+    return fail(BRX_ERR_INVALID_ARGUMENT, buf);
+}
+
+// everything the rule reads, as the call got it
+static BrxTakeArgs rec_args(const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                            const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,
+                            uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m) {
+    BrxTakeArgs a;
+    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
+    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
+    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the call its own)
+    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    return a;
+}
+
+// The refusals in front of a call's own: `own_flags` are the bits the call takes beside BRX_TAKE_NO_DELIM and BRX_TAKE_TRIM_CR.
+static int rec_check_head(const char *call, const brx_ctx *c, const BrxTakeArgs &a, uint32_t own_flags) {
+    if (!c) return refuse(call, "ctx is NULL");
+    if (a.flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | own_flags)) return refuse(call, "unknown flag bits");
+    if ((a.flags & BRX_TAKE_TRIM_CR) && !(a.flags & BRX_TAKE_NO_DELIM)) return refuse(call, "BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
+    if (a.delim_len == 0 || a.delim_len > BRX_TAKE_MAX_DELIM) return refuse(call, "delim_len is not 1 .. 16");
+    if ((a.sel_stream == nullptr) != (a.sel_rec == nullptr)) return refuse(call, "sel_stream and sel_rec go together");
+    return BRX_SUCCESS;
+}
+
+// The refusals behind a call's own and behind the m == 0 exit; `dst` and `total` of a call with a destination, else NULL and 0.
+static int rec_check_tail(const char *call, const BrxTakeArgs &a, const uint8_t *dst, uint64_t total) {
+    if (!a.out_off || !a.len || !a.count || !a.pos_off) return refuse(call, "NULL table");
+    if (!a.pos && a.n_pos > 0) return refuse(call, "pos is NULL with n_pos > 0");
+    if (!a.sel_stream && a.n == 0) return refuse(call, "all-records mode with n = 0");
+    if (brx_ix_max_tiles(a.n, a.span) > (uint64_t)1 << 40) return refuse(call, "span out of range");
+    // the grids follow from m and total alone
+    if ((a.m + 255u) / 256u > 0x7fffffffull) return refuse(call, "m out of range");
+    if (dst && (total > (uint64_t)1 << 62 || brx_take_chunks(total, dst) > 0x7fffffffull))
+        return refuse(call, "total out of range (more than 8 TiB)");
+    return BRX_SUCCESS;
 }
 
 // ---- selected records of the decoded streams of a batch (brx_take.hip) ------------------------------------------------------
@@ -1559,40 +1575,18 @@ extern "C" int brx_take_batch(brx_ctx *c, const uint8_t *out, const uint64_t *ou
                               uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t *rec_len,
                               const uint64_t *dst_off, uint8_t *dst, uint64_t total, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: ctx is NULL");
-    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: unknown flag bits");
-    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
-    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: delim_len is not 1 .. 16");
-    if ((sel_stream == nullptr) != (sel_rec == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: sel_stream and sel_rec go together");
-    if ((dst_off == nullptr) != (dst == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: dst_off and dst go together");
-    if (!dst && !rec_len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: rec_len is NULL in size mode");
+    const char *call = "brx_take_batch";
+    const BrxTakeArgs a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m);
+    if (int rc = rec_check_head(call, c, a, 0u)) return rc;
+    if ((dst_off == nullptr) != (dst == nullptr)) return refuse(call, "dst_off and dst go together");
+    if (!dst && !rec_len) return refuse(call, "rec_len is NULL in size mode");
     if (m == 0) return BRX_SUCCESS;
-    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: NULL table");
-    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: pos is NULL with n_pos > 0");
-    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: all-records mode with n = 0");
-    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: span out of range");
-    // the grids follow from m and total alone
-    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: m out of range");
-    if (dst && (total > (uint64_t)1 << 62 || brx_take_chunks(total, dst) > 0x7fffffffull))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_take_batch: total out of range (more than 8 TiB)");
-    BrxTakeArgs a;
-    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
-    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
-    a.delim_len = delim_len; a.flags = flags;
-    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (int rc = rec_check_tail(call, a, dst, total)) return rc;
+    return run_locked(c, hip_stream, [&](hipStream_t st) {
         if (rec_len) brx_launch_take_size(a, rec_len, st);
         if (dst) brx_launch_take_fill(a, dst_off, dst, total, st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+        return launched();
+    });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1602,36 +1596,14 @@ extern "C" int brx_hash_batch(brx_ctx *c, const uint8_t *out, const uint64_t *ou
                               uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t seed, uint64_t *hash,
                               uint64_t *rec_len, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: ctx is NULL");
-    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: unknown flag bits");
-    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
-    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: delim_len is not 1 .. 16");
-    if ((sel_stream == nullptr) != (sel_rec == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: sel_stream and sel_rec go together");
-    if (!hash) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: hash is NULL");
+    const char *call = "brx_hash_batch";
+    const BrxTakeArgs a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m);
+    if (int rc = rec_check_head(call, c, a, 0u)) return rc;
+    if (!hash) return refuse(call, "hash is NULL");
     if (m == 0) return BRX_SUCCESS;
-    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: NULL table");
-    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: pos is NULL with n_pos > 0");
-    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: all-records mode with n = 0");
-    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: span out of range");
-    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_hash_batch: m out of range"); // the grid follows from m alone
-    BrxTakeArgs a;
-    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
-    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
-    a.delim_len = delim_len; a.flags = flags;
-    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    if (int rc = rec_check_tail(call, a, nullptr, 0)) return rc;
     const BrxHashKeys k = brx_hash_keys(seed); // K, K^2, K^3, K^4, K^256: launch arguments, no table
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        brx_launch_hash(a, k, hash, rec_len, st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_hash(a, k, hash, rec_len, st); return launched(); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1641,39 +1613,16 @@ extern "C" int brx_parse_batch(brx_ctx *c, const uint8_t *out, const uint64_t *o
                                uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint32_t kind, uint32_t scale,
                                uint8_t quote, int64_t *val, uint8_t *status, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: ctx is NULL");
-    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | BRX_PARSE_SPACES | BRX_PARSE_QUOTED))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: unknown flag bits");
-    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
-    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: delim_len is not 1 .. 16");
-    if ((sel_stream == nullptr) != (sel_rec == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: sel_stream and sel_rec go together");
-    if (kind > BRX_PARSE_HEX) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: kind is not BRX_PARSE_INT, _DEC or _HEX");
+    const char *call = "brx_parse_batch";
+    const BrxTakeArgs a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m);
+    if (int rc = rec_check_head(call, c, a, BRX_PARSE_SPACES | BRX_PARSE_QUOTED)) return rc;
+    if (kind > BRX_PARSE_HEX) return refuse(call, "kind is not BRX_PARSE_INT, _DEC or _HEX");
     if (scale > BRX_PARSE_MAX_SCALE || (scale && kind != BRX_PARSE_DEC))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: scale is not 0 .. 18, or not 0 with BRX_PARSE_INT / BRX_PARSE_HEX");
-    if (!val || !status) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: val or status is NULL");
+        return refuse(call, "scale is not 0 .. 18, or not 0 with BRX_PARSE_INT / BRX_PARSE_HEX");
+    if (!val || !status) return refuse(call, "val or status is NULL");
     if (m == 0) return BRX_SUCCESS;
-    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: NULL table");
-    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: pos is NULL with n_pos > 0");
-    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: all-records mode with n = 0");
-    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: span out of range");
-    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_batch: m out of range"); // the grid follows from m alone
-    BrxTakeArgs a;
-    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
-    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
-    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the parse its own two)
-    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        brx_launch_parse(a, kind, scale, quote, val, status, st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    if (int rc = rec_check_tail(call, a, nullptr, 0)) return rc;
+    return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_parse(a, kind, scale, quote, val, status, st); return launched(); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1683,36 +1632,14 @@ extern "C" int brx_parse_f64_batch(brx_ctx *c, const uint8_t *out, const uint64_
                                    uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint8_t quote, double *val,
                                    uint8_t *status, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: ctx is NULL");
-    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | BRX_PARSE_SPACES | BRX_PARSE_QUOTED | BRX_PARSE_WORDS))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: unknown flag bits");
-    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
-    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: delim_len is not 1 .. 16");
-    if ((sel_stream == nullptr) != (sel_rec == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: sel_stream and sel_rec go together");
-    if (!val || !status) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: val or status is NULL");
+    const char *call = "brx_parse_f64_batch";
+    const BrxTakeArgs a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m);
+    if (int rc = rec_check_head(call, c, a, BRX_PARSE_SPACES | BRX_PARSE_QUOTED | BRX_PARSE_WORDS)) return rc;
+    if (!val || !status) return refuse(call, "val or status is NULL");
     if (m == 0) return BRX_SUCCESS;
-    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: NULL table");
-    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: pos is NULL with n_pos > 0");
-    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: all-records mode with n = 0");
-    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: span out of range");
-    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_f64_batch: m out of range"); // the grid follows from m alone
-    BrxTakeArgs a;
-    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
-    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
-    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the parse its own three)
-    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        brx_launch_parse_f64(a, quote, (uint64_t *)val, status, st); // (the kernel writes bit patterns: no double arithmetic on the device)
-        HIP_TRY(hipGetLastError());
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    if (int rc = rec_check_tail(call, a, nullptr, 0)) return rc;
+    uint64_t *bits = (uint64_t *)val; // (the kernel writes bit patterns: no double arithmetic on the device)
+    return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_parse_f64(a, quote, bits, status, st); return launched(); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1722,39 +1649,15 @@ extern "C" int brx_parse_time_batch(brx_ctx *c, const uint8_t *out, const uint64
                                     uint32_t flags, const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint32_t kind, uint32_t scale,
                                     uint8_t quote, int64_t *val, uint8_t *status, int16_t *zone, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: ctx is NULL");
-    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | BRX_PARSE_SPACES | BRX_PARSE_QUOTED))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: unknown flag bits");
-    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
-    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: delim_len is not 1 .. 16");
-    if ((sel_stream == nullptr) != (sel_rec == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: sel_stream and sel_rec go together");
-    if (kind > BRX_TIME_STAMP) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: kind is not BRX_TIME_DATE, _TIME or _STAMP");
-    if (scale > BRX_TIME_MAX_SCALE || (scale && kind == BRX_TIME_DATE))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: scale is not 0 .. 9, or not 0 with BRX_TIME_DATE");
-    if (!val || !status) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: val or status is NULL");
+    const char *call = "brx_parse_time_batch";
+    const BrxTakeArgs a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m);
+    if (int rc = rec_check_head(call, c, a, BRX_PARSE_SPACES | BRX_PARSE_QUOTED)) return rc;
+    if (kind > BRX_TIME_STAMP) return refuse(call, "kind is not BRX_TIME_DATE, _TIME or _STAMP");
+    if (scale > BRX_TIME_MAX_SCALE || (scale && kind == BRX_TIME_DATE)) return refuse(call, "scale is not 0 .. 9, or not 0 with BRX_TIME_DATE");
+    if (!val || !status) return refuse(call, "val or status is NULL");
     if (m == 0) return BRX_SUCCESS;
-    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: NULL table");
-    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: pos is NULL with n_pos > 0");
-    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: all-records mode with n = 0");
-    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: span out of range");
-    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_parse_time_batch: m out of range"); // the grid follows from m alone
-    BrxTakeArgs a;
-    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
-    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
-    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the parse its own two)
-    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        brx_launch_parse_time(a, kind, scale, quote, val, status, zone, st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    if (int rc = rec_check_tail(call, a, nullptr, 0)) return rc;
+    return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_parse_time(a, kind, scale, quote, val, status, zone, st); return launched(); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
@@ -1765,45 +1668,20 @@ extern "C" int brx_unescape_batch(brx_ctx *c, const uint8_t *out, const uint64_t
                                   uint32_t quote, uint32_t escape, uint64_t *text_len, uint8_t *status, const uint64_t *dst_off, uint8_t *dst,
                                   uint64_t total, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: ctx is NULL");
-    if (flags & ~(BRX_TAKE_NO_DELIM | BRX_TAKE_TRIM_CR | BRX_PARSE_SPACES))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: unknown flag bits");
-    if ((flags & BRX_TAKE_TRIM_CR) && !(flags & BRX_TAKE_NO_DELIM))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: BRX_TAKE_TRIM_CR without BRX_TAKE_NO_DELIM");
-    if (delim_len == 0 || delim_len > BRX_TAKE_MAX_DELIM) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: delim_len is not 1 .. 16");
-    if ((sel_stream == nullptr) != (sel_rec == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: sel_stream and sel_rec go together");
-    if (dialect > BRX_TEXT_BACKSLASH) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: dialect is not BRX_TEXT_CSV, _JSON or _BACKSLASH");
-    if (quote > 255u || escape > 255u) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: quote or escape is not a byte value");
-    if (dialect == BRX_TEXT_JSON && quote == escape) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: BRX_TEXT_JSON with quote == escape");
-    if ((dst_off == nullptr) != (dst == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: dst_off and dst go together");
-    if (!dst && (!text_len || !status)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: text_len or status is NULL in size mode");
+    const char *call = "brx_unescape_batch";
+    const BrxTakeArgs a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, delim_len, flags, sel_stream, sel_rec, m);
+    if (int rc = rec_check_head(call, c, a, BRX_PARSE_SPACES)) return rc;
+    if (dialect > BRX_TEXT_BACKSLASH) return refuse(call, "dialect is not BRX_TEXT_CSV, _JSON or _BACKSLASH");
+    if (quote > 255u || escape > 255u) return refuse(call, "quote or escape is not a byte value");
+    if (dialect == BRX_TEXT_JSON && quote == escape) return refuse(call, "BRX_TEXT_JSON with quote == escape");
+    if ((dst_off == nullptr) != (dst == nullptr)) return refuse(call, "dst_off and dst go together");
+    if (!dst && (!text_len || !status)) return refuse(call, "text_len or status is NULL in size mode");
     if (m == 0) return BRX_SUCCESS;
-    if (!out_off || !len || !count || !pos_off) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: NULL table");
-    if (!pos && n_pos > 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: pos is NULL with n_pos > 0");
-    if (!sel_stream && n == 0) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: all-records mode with n = 0");
-    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: span out of range");
-    if ((m + 255u) / 256u > 0x7fffffffull) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: m out of range"); // the grid follows from m alone
-    if (dst && (total > (uint64_t)1 << 62 || brx_take_chunks(total, dst) > 0x7fffffffull))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_unescape_batch: total out of range (more than 8 TiB)");
-    BrxTakeArgs a;
-    a.out = out; a.out_off = out_off; a.len = len; a.n = n; a.span = span;
-    a.count = count; a.pos_off = pos_off; a.pos = pos; a.n_pos = n_pos;
-    a.delim_len = delim_len; a.flags = flags; // (the rule reads its own two bits, the text its own one)
-    a.sel_stream = sel_stream; a.sel_rec = sel_rec; a.m = m;
+    if (int rc = rec_check_tail(call, a, dst, total)) return rc;
     BrxTextArgs x;
     x.dialect = dialect; x.q = quote; x.e = escape;
     x.text_len = text_len; x.status = status; x.dst_off = dst_off; x.dst = dst; x.total = total;
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIP_TRY(hipSetDevice(c->device));
-        st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-        brx_launch_unescape(a, x, st);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!hip_stream) HIP_TRY(hipStreamSynchronize(st));
-    return BRX_SUCCESS;
+    return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_unescape(a, x, st); return launched(); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 

@@ -6,7 +6,9 @@
 //   uint8_t  M::ld8(const uint8_t *p)             one arena byte
 //   BrxTake128 M::ld128(const uint8_t *p)         16 arena bytes at any alignment (only where the caller proved them inside the arena)
 //   void     M::st8(uint8_t *p, uint8_t v)        one destination byte
-//   void     M::st128(uint8_t *p, BrxTake128 v)   16 destination bytes, p 16-byte aligned
+//   void     M::st128(uint8_t *p, BrxTake128 v)   16 destination bytes, p 16-byte aligned (on the device BrxRecMemAligned of
+//                                                 brx_record_dev.h: one aligned dwordx4; brx_unescape.h stores at any address, through
+//                                                 BrxRecMemUnaligned)
 // The tables (out_off, len, count, pos_off, pos, sel_*, dst_off) are read directly: the caller owns their sizes.
 #ifndef BRX_TAKE_H
 #define BRX_TAKE_H

@@ -1,6 +1,7 @@
 // brx_take.hip -- brx_take_batch: the selected records of the decoded streams of a batch, as lengths (size kernel) or as bytes in a
 // destination (fill kernel).  The rule, the descriptor of an entry and the assembly of a destination unit are plain C++ in brx_take.h,
-// shared with tools/take_emu.cpp; this file holds what is HIP: the memory policy, the descriptor window in LDS and the launches.
+// shared with tools/take_emu.cpp; this file holds what is HIP and its own: the descriptor window in LDS and the launches.  What the
+// record kernels share on the device is brx_record_dev.h.
 //
 // Size kernel: one thread per selection entry.
 // Fill kernel: DESTINATION-centric, so its cost does not depend on how small the records are.  One wavefront (a workgroup of its own,
@@ -10,38 +11,19 @@
 // spans: one aligned dwordx4 store where the unit is covered, byte stores where it is not.  Source bytes come by unaligned 16-byte
 // loads wherever those lie inside the arena.  A chunk in which more than 64 entries start refills the window; a record longer than a
 // chunk is served by several waves independently.  No scratch, no atomics, no inter-workgroup traffic.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "brx_take.h"
+#include "brx_record_dev.h"
 
-struct __attribute__((packed, aligned(1))) brx_take_u128u { uint32_t w[4]; };
-
-struct BrxTakeDevMem {
-    __device__ __forceinline__ uint8_t ld8(const uint8_t *p) { return *p; }
-    __device__ __forceinline__ BrxTake128 ld128(const uint8_t *p) {
-        const brx_take_u128u v = *(const brx_take_u128u *)p;
-        BrxTake128 r;
-        r.lo = (uint64_t)v.w[0] | ((uint64_t)v.w[1] << 32);
-        r.hi = (uint64_t)v.w[2] | ((uint64_t)v.w[3] << 32);
-        return r;
-    }
-    __device__ __forceinline__ void st8(uint8_t *p, uint8_t v) { *p = v; }
-    __device__ __forceinline__ void st128(uint8_t *p, BrxTake128 v) {
-        *(uint4 *)p = make_uint4((uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32));
-    }
-};
-
-__global__ __launch_bounds__(256) void brx_take_size_kernel(BrxTakeArgs a, uint64_t *__restrict__ rec_len) {
-    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+__global__ __launch_bounds__(BRX_REC_BLOCK) void brx_take_size_kernel(BrxTakeArgs a, uint64_t *__restrict__ rec_len) {
+    const uint64_t j = brx_rec_entry();
     if (j >= a.m) return;
-    BrxTakeDevMem mem;
+    BrxRecMem mem;
     rec_len[j] = brx_take_entry_record(mem, a, j).len;
 }
 
 __global__ __launch_bounds__(64) void brx_take_fill_kernel(BrxTakeArgs a, const uint64_t *__restrict__ dst_off, uint8_t *dst,
                                                            uint64_t total) {
     __shared__ uint64_t w_start[BRX_TAKE_WINDOW], w_src[BRX_TAKE_WINDOW], w_cnt[BRX_TAKE_WINDOW];
-    BrxTakeDevMem mem;
+    BrxRecMemAligned mem; // (a unit goes out at a 16-byte aligned address)
     const uint32_t lane = threadIdx.x;
     const uint32_t phase = (uint32_t)((uintptr_t)dst & 15u);
     uint8_t *dst_al = dst - phase;
@@ -80,9 +62,8 @@ __global__ __launch_bounds__(64) void brx_take_fill_kernel(BrxTakeArgs a, const 
 }
 
 void brx_launch_take_size(const BrxTakeArgs &a, uint64_t *rec_len, void *hip_stream) {
-    const uint64_t blocks = (a.m + 255u) / 256u;
-    if (blocks == 0) return;
-    hipLaunchKernelGGL(brx_take_size_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, a, rec_len);
+    if (a.m == 0) return;
+    hipLaunchKernelGGL(brx_take_size_kernel, dim3(brx_rec_blocks(a.m)), dim3(BRX_REC_BLOCK), 0, (hipStream_t)hip_stream, a, rec_len);
 }
 
 void brx_launch_take_fill(const BrxTakeArgs &a, const uint64_t *dst_off, uint8_t *dst, uint64_t total, void *hip_stream) {

@@ -1,56 +1,31 @@
 // brx_unescape.hip -- brx_unescape_batch: every selected record of the decoded streams of a batch as the string it spells (CSV quoting,
 // JSON string escapes, backslash escapes), as lengths and statuses (size mode) or as bytes in a destination (fill mode).  The plan of a
 // record, the classification of a unit, the escapes, the walk of a unit and the lane path are plain C++ in brx_unescape.h, shared with
-// tools/unescape_emu.cpp; the record rule is that of brx_take.h.  This file holds what is HIP: the memory policy, the ballot over the
-// long records, the carries and the sums across the wave, and the launch.
+// tools/unescape_emu.cpp; the record rule is that of brx_take.h.  This file holds what is HIP and its own: the ballot over the long
+// records, the carries and the sums across the wave, and the launch.  What the record kernels share on the device is brx_record_dev.h
+// (DESIGN.md 17.1).
 //
 // One lane owns one entry.  A record whose walk range is shorter than BRX_TEXT_LONG is walked by its lane alone, unit by unit.  The
 // lanes with longer ones leave them out; the wave then takes those one at a time in a wave-uniform loop over their ballot, lane l on
 // unit 64 row + l: the run parity goes from lane to lane by a ballot and a shuffle, a lane's place in the text by a prefix sum of the
 // lanes' output counts.  The kernel is compiled once per dialect, so that the unit walk holds one dialect's tokens only.  No scratch,
 // no atomics, no LDS.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "brx_record_dev.h"
 #include "brx_unescape.h"
-
-struct __attribute__((packed, aligned(1))) brx_text_u128u { uint32_t w[4]; };
-
-struct BrxTextDevMem {
-    __device__ __forceinline__ uint8_t ld8(const uint8_t *p) { return *p; }
-    __device__ __forceinline__ BrxTake128 ld128(const uint8_t *p) {
-        const brx_text_u128u v = *(const brx_text_u128u *)p;
-        BrxTake128 r;
-        r.lo = (uint64_t)v.w[0] | ((uint64_t)v.w[1] << 32);
-        r.hi = (uint64_t)v.w[2] | ((uint64_t)v.w[3] << 32);
-        return r;
-    }
-    __device__ __forceinline__ void st8(uint8_t *p, uint8_t v) { *p = v; }
-    __device__ __forceinline__ void st128(uint8_t *p, BrxTake128 v) {
-        brx_text_u128u w;
-        w.w[0] = (uint32_t)v.lo; w.w[1] = (uint32_t)(v.lo >> 32); w.w[2] = (uint32_t)v.hi; w.w[3] = (uint32_t)(v.hi >> 32);
-        *(brx_text_u128u *)p = w;
-    }
-};
 
 // x of lane `src` as every lane's own copy, in a vector register.  What the unit walk reads of the record in hand (its address, its
 // range, its room) is taken this way and not by readlane: as scalars, together with the saved execution masks of the walk's branches,
-// they do not fit the scalar registers of a wave, and the compiler spills them.  Only the row loop's own bounds are scalars.
+// they do not fit the scalar registers of a wave, and the compiler spills them.  Only the row loop's own bounds are scalars
+// (brx_rec_bcast).
 __device__ __forceinline__ uint64_t brx_text_copy(uint64_t x, uint32_t src) { return (uint64_t)__shfl((unsigned long long)x, (int)src, 64); }
-// x of lane `src` (wave-uniform) in every lane, as a scalar
-__device__ __forceinline__ uint32_t brx_text_bcast32(uint32_t x, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)src);
-}
-__device__ __forceinline__ uint64_t brx_text_bcast(uint64_t x, uint32_t src) {
-    return (uint64_t)brx_text_bcast32((uint32_t)x, src) | ((uint64_t)brx_text_bcast32((uint32_t)(x >> 32), src) << 32);
-}
 
 template <uint32_t DIALECT>
-__global__ __launch_bounds__(256) void brx_unescape_kernel(BrxTakeArgs a, BrxTextArgs x) {
+__global__ __launch_bounds__(BRX_REC_BLOCK) void brx_unescape_kernel(BrxTakeArgs a, BrxTextArgs x) {
     // every lane stays to the end: the loop over the long records needs the whole wave
-    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t j = brx_rec_entry();
     const uint32_t lane = threadIdx.x & 63u;
     constexpr uint32_t MODE = DIALECT + 1u; // BRX_TEXT_M_* of a record that is not copied as it stands
-    BrxTextDevMem mem;
+    BrxRecMemUnaligned mem; // (a text's bytes go out wherever they fall)
     BrxTakeRec r = {0, 0};
     BrxTextPlan p = {0, 0, BRX_TEXT_M_COPY, BRX_TEXT_S_BARE};
     BrxTextRoom d = {0, 0};
@@ -74,8 +49,8 @@ __global__ __launch_bounds__(256) void brx_unescape_kernel(BrxTakeArgs a, BrxTex
         BrxTextPlan wp;
         wp.ws = (int64_t)brx_text_copy((uint64_t)p.ws, owner);
         wp.we = (int64_t)brx_text_copy((uint64_t)p.we, owner);
-        const int64_t u_ws = (int64_t)brx_text_bcast((uint64_t)p.ws, owner), u_we = (int64_t)brx_text_bcast((uint64_t)p.we, owner);
-        wp.mode = brx_text_bcast32(p.mode, owner);
+        const int64_t u_ws = (int64_t)brx_rec_bcast((uint64_t)p.ws, owner), u_we = (int64_t)brx_rec_bcast((uint64_t)p.we, owner);
+        wp.mode = brx_rec_bcast32(p.mode, owner);
         wp.status = 0;
         uint8_t *dstp = (uint8_t *)brx_text_copy((uint64_t)(uintptr_t)d.dstp, owner);
         const uint64_t room = brx_text_copy(d.room, owner);
@@ -89,7 +64,7 @@ __global__ __launch_bounds__(256) void brx_unescape_kernel(BrxTakeArgs a, BrxTex
             const int32_t src = brx_text_pin_lane(__ballot(u.em != 0xFFFFu), lane);
             const uint32_t E = brx_text_row_e(u.em, e0, src, (uint32_t)__shfl((int)e0, src < 0 ? 0 : src, 64), carry);
             const uint32_t Eprev = brx_text_row_prev(lane, (uint32_t)__shfl_up((int)E, 1, 64), carry);
-            carry = brx_text_row_carry(brx_text_bcast32(E, 63u));
+            carry = brx_text_row_carry(brx_rec_bcast32(E, 63u));
             const BrxTextOut o = brx_text_unit<MODE>(mem, rec, L, wp, x.q, x.e, b, u, Eprev | (E << 16));
             uint32_t sum = o.cnt; // inclusive prefix sum of the lanes' counts
             for (int s = 1; s < 64; s <<= 1) {
@@ -97,7 +72,7 @@ __global__ __launch_bounds__(256) void brx_unescape_kernel(BrxTakeArgs a, BrxTex
                 if (lane >= (uint32_t)s) sum += y;
             }
             brx_text_store(mem, dstp, brx_text_row_at(base, sum, o.cnt), room, o);
-            base += brx_text_bcast32(sum, 63u);
+            base += brx_rec_bcast32(sum, 63u);
             bad |= __ballot(o.bad != 0u) != 0u;
             closed |= __ballot(o.closed != 0u) != 0u;
         }
@@ -110,9 +85,8 @@ __global__ __launch_bounds__(256) void brx_unescape_kernel(BrxTakeArgs a, BrxTex
 }
 
 void brx_launch_unescape(const BrxTakeArgs &a, const BrxTextArgs &x, void *hip_stream) {
-    const uint64_t blocks = (a.m + 255u) / 256u;
-    if (blocks == 0) return;
-    const dim3 grid((unsigned)blocks), block(256);
+    if (a.m == 0) return;
+    const dim3 grid(brx_rec_blocks(a.m)), block(BRX_REC_BLOCK);
     if (x.dialect == BRX_TEXT_D_CSV) hipLaunchKernelGGL(brx_unescape_kernel<BRX_TEXT_D_CSV>, grid, block, 0, (hipStream_t)hip_stream, a, x);
     else if (x.dialect == BRX_TEXT_D_JSON) hipLaunchKernelGGL(brx_unescape_kernel<BRX_TEXT_D_JSON>, grid, block, 0, (hipStream_t)hip_stream, a, x);
     else hipLaunchKernelGGL(brx_unescape_kernel<BRX_TEXT_D_BACKSLASH>, grid, block, 0, (hipStream_t)hip_stream, a, x);
