@@ -47,6 +47,9 @@ TIME_NO_ZONE = -32768  # BRX_TIME_NO_ZONE
 TEXT_CSV, TEXT_JSON, TEXT_BACKSLASH = 0, 1, 2  # BRX_TEXT_CSV / _JSON / _BACKSLASH (brx_unescape_batch)
 TEXT_DIALECTS = {"csv": TEXT_CSV, "json": TEXT_JSON, "backslash": TEXT_BACKSLASH}
 TEXT_OK, TEXT_BARE, TEXT_NULL, TEXT_BAD = 0, 1, 2, 3  # BRX_TEXT_OK ... (the status byte)
+MEMBER_MAX_NAMES, MEMBER_MAX_NAME, MEMBER_MAX_KEY = 8, 32, 64  # BRX_MEMBER_MAX_NAMES ... (brx_member_batch)
+MEMBER_MISSING, MEMBER_SCALAR, MEMBER_OBJECT, MEMBER_ARRAY, MEMBER_BAD = 0, 1, 2, 3, 4  # BRX_MEMBER_MISSING ... (the kind byte)
+MEMBER_LONG_KEY, MEMBER_ESCAPED_KEY, MEMBER_UNBALANCED = 1, 2, 4  # BRX_MEMBER_LONG_KEY ... (the bits of line_flags)
 
 
 class BrxError(RuntimeError):
@@ -127,6 +130,9 @@ def load_library():
                       ("brx_unescape_batch", [U32, U32, U32, P, P, P, P, U64, P])):
         getattr(L, name).restype = ctypes.c_int
         getattr(L, name).argtypes = rec + own
+    L.brx_member_batch.restype = ctypes.c_int
+    L.brx_member_batch.argtypes = [P, P, P, P, U32, U64, P, P, P, P, U64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), U32, P, P, U64,
+                                   P, P, P, P, P]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -184,7 +190,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
                     "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch",
-                    "brx_parse_batch", "brx_parse_time_batch", "brx_unescape_batch"]
+                    "brx_parse_batch", "brx_parse_time_batch", "brx_unescape_batch", "brx_member_batch"]
 # Exported names with a digit in them.  They are kept apart because tests/test_abi.py compares EXPORTED_SYMBOLS with the names it reads
 # from include/brx.h by the pattern brx_[a-z_]+, which such a name does not match; tests/test_parse_f64_abi.py holds this list to the
 # header and to the library.
@@ -805,6 +811,66 @@ class Context:
         dst, dst_off = _rec_gather(out, stream, r.m, len_buf[:r.m], stride,
                                    lambda off, dst, total: self.unescape_batch_device(*head, *sizes, off, dst, total, hip_stream=r.hs))
         return dst, dst_off, len_buf[:r.m], status_buf[:r.m]
+
+    def member_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, what_ptr, n_pos, names,
+                            lines_ptr, line_off_ptr=None, m=0, sel_stream_ptr=None, sel_rec_ptr=None, kind_ptr=None, line_flags_ptr=None,
+                            hip_stream=None):
+        """brx_member_batch on raw device pointers: the named members of the JSON Lines objects of a batch, under the positions count /
+        pos_off / pos / what of a fill-mode index_set_batch call with delims b'{}[]:,\\n'.  `names`: a sequence of 1 .. 8 distinct
+        bytes objects of 1 .. 32 bytes, host memory, taken during the call.  Count mode (line_off_ptr, sel_stream_ptr, sel_rec_ptr and
+        kind_ptr None): lines[i] (uint64) = line feeds outside strings of stream i, plus 1.  Fill mode: entry (q, j) at q * m + j, line
+        j = line_off[i] + r: sel_stream (uint32), sel_rec (uint64) and kind (uint8, MEMBER_MISSING ... MEMBER_BAD) of the last depth-1
+        member of the line whose key is names[q]; line_flags[j] (uint8, may be None) = MEMBER_LONG_KEY | MEMBER_ESCAPED_KEY |
+        MEMBER_UNBALANCED.  Nothing at or beyond n_names * m is written."""
+        names = [bytes(x) for x in names]
+        packed = b"".join(x[:MEMBER_MAX_NAME].ljust(MEMBER_MAX_NAME, b"\0") for x in names)
+        lens = (ctypes.c_uint32 * max(len(names), 1))(*[len(x) for x in names])
+        rc = self._lib.brx_member_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, what_ptr, n_pos,
+                                        packed, lens, len(names), lines_ptr, line_off_ptr, m, sel_stream_ptr, sel_rec_ptr, kind_ptr,
+                                        line_flags_ptr, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_member_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def member_batch(self, out, out_off, out_len, count, pos_off, pos, what, names, stream=None):
+        """The named members of the JSON Lines objects of a batch as selections for the record calls, found on the device.  out, out_off,
+        out_len and stream as for index_batch; count, pos_off, pos, what as index_set_batch(delims=b'{}[]:,\\n') returned them; names:
+        1 .. 8 distinct keys (bytes, 1 .. 32 of them each, compared bytewise with what stands between the key's quotes).
+        Returns (lines, line_off, sel_stream, sel_rec, kind, line_flags): lines[i] = lines of stream i (the last one is what follows
+        the last line feed), line_off its exclusive prefix sum, M = sum(lines); sel_stream (int32), sel_rec (int64) and kind (uint8) of
+        shape [len(names), M]: row q is the selection of names[q] for a record call, entry j its value in line j -- the LAST depth-1
+        member with that key, as json.loads has it; kind MEMBER_SCALAR (the record is the value), MEMBER_OBJECT / MEMBER_ARRAY (a nested
+        value starts there), MEMBER_BAD, or MEMBER_MISSING (sel_rec -1: selects nothing, so parse_batch gives PARSE_EMPTY and
+        unescape_batch an empty text); line_flags[j] (uint8): MEMBER_LONG_KEY, MEMBER_ESCAPED_KEY, MEMBER_UNBALANCED.  A count-mode
+        call, a cumsum on the device, one scalar read back (the total of lines), a fill-mode call.  The ids and texts of a batch whose
+        lines carry "id" and "text" in any order, among other keys:
+            count, _, pos_off, pos, what = ctx.index_set_batch(out, out_off, out_len, delims=b'{}[]:,\\n')
+            lines, line_off, ss, sr, kind, flags = ctx.member_batch(out, out_off, out_len, count, pos_off, pos, what, [b"id", b"text"])
+            ids, st = ctx.parse_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=ss[0], sel_rec=sr[0], spaces=True)
+            dst, dst_off, text_len, st = ctx.unescape_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=ss[1],
+                                                            sel_rec=sr[1], dialect="json", spaces=True)"""
+        import torch
+        n, Q = int(out_len.numel()), len(names)
+        dev = out.device
+        hs = stream.cuda_stream if stream is not None else None
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            lines = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]
+        _rec_sync(out, stream)
+        head = (out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(), pos_off.data_ptr(),
+                pos.data_ptr(), what.data_ptr(), int(pos.numel()), names)
+        self.member_batch_device(*head, lines.data_ptr(), hip_stream=hs)
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            ends = torch.cumsum(lines, 0)
+            line_off = ends - lines
+            M = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
+            sel_stream = torch.empty((Q, max(M, 1)), dtype=torch.int32, device=dev)
+            sel_rec = torch.empty((Q, max(M, 1)), dtype=torch.int64, device=dev)
+            kind = torch.empty((Q, max(M, 1)), dtype=torch.uint8, device=dev)
+            line_flags = torch.empty(max(M, 1), dtype=torch.uint8, device=dev)
+        if M > 0:  # (the buffers are exactly [Q, M]: entry (q, j) is at q * M + j)
+            _rec_sync(out, stream)
+            self.member_batch_device(*head, None, line_off.data_ptr(), M, sel_stream.data_ptr(), sel_rec.data_ptr(), kind.data_ptr(),
+                                     line_flags.data_ptr(), hip_stream=hs)
+        return lines, line_off, sel_stream[:, :M], sel_rec[:, :M], kind[:, :M], line_flags[:M]
 
     def parse_f64_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                                sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream=None):

@@ -39,6 +39,7 @@
 #include "brx_parse_f64.h"
 #include "brx_parse_time.h"
 #include "brx_unescape.h"
+#include "brx_member.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -244,6 +245,8 @@ struct brx_ctx {
     PassRing index_set_ring;
     // brx_find_batch (brx_find.hip): scratch (ticket counters, tile prefix sums, per-tile counts)
     PassRing find_ring;
+    // brx_member_batch (brx_member.hip): scratch (tile prefix sums, lines per stream, per-tile summaries and carries)
+    PassRing member_ring;
     std::mutex stage_mu;                          // the readers' pinned output staging: free buffers, bytes allocated
     std::vector<uint8_t *> stage_free;
     size_t stage_bytes = 0;
@@ -334,6 +337,7 @@ static void ctx_release(brx_ctx *c) {
     ring_free(c->index_escaped_ring);
     ring_free(c->index_set_ring);
     ring_free(c->find_ring);
+    ring_free(c->member_ring);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->ev_in)
@@ -1682,6 +1686,57 @@ extern "C" int brx_unescape_batch(brx_ctx *c, const uint8_t *out, const uint64_t
     x.dialect = dialect; x.q = quote; x.e = escape;
     x.text_len = text_len; x.status = status; x.dst_off = dst_off; x.dst = dst; x.total = total;
     return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_unescape(a, x, st); return launched(); });
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- named members of the JSON Lines objects of a batch as selections for the record calls (brx_member.hip) ------------------
+extern "C" int brx_member_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                                const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                                const uint8_t *names, const uint32_t *name_len, uint32_t n_names, uint64_t *lines, const uint64_t *line_off,
+                                uint64_t m, uint32_t *sel_stream, uint64_t *sel_rec, uint8_t *kind, uint8_t *line_flags, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    const char *call = "brx_member_batch";
+    static_assert(BRX_MB_MAX_NAMES == BRX_MEMBER_MAX_NAMES && BRX_MB_MAX_NAME == BRX_MEMBER_MAX_NAME && BRX_MB_MAX_KEY == BRX_MEMBER_MAX_KEY &&
+                  BRX_MB_K_MISSING == BRX_MEMBER_MISSING && BRX_MB_K_SCALAR == BRX_MEMBER_SCALAR && BRX_MB_K_OBJECT == BRX_MEMBER_OBJECT &&
+                  BRX_MB_K_ARRAY == BRX_MEMBER_ARRAY && BRX_MB_K_BAD == BRX_MEMBER_BAD && BRX_MB_F_LONG_KEY == BRX_MEMBER_LONG_KEY &&
+                  BRX_MB_F_ESCAPED_KEY == BRX_MEMBER_ESCAPED_KEY && BRX_MB_F_UNBALANCED == BRX_MEMBER_UNBALANCED, "the kernels' values are brx.h's");
+    if (!c) return refuse(call, "ctx is NULL");
+    if (!names || !name_len) return refuse(call, "names or name_len is NULL");
+    if (n_names == 0 || n_names > BRX_MEMBER_MAX_NAMES) return refuse(call, "n_names is not 1 .. 8");
+    for (uint32_t q = 0; q < n_names; q++)
+        if (name_len[q] == 0 || name_len[q] > BRX_MEMBER_MAX_NAME) return refuse(call, "a name_len is not 1 .. 32");
+    // the names as the kernels take them: launch arguments (read here: the caller may reuse `names` at once)
+    BrxMbNames nm;
+    memset(&nm, 0, sizeof nm);
+    nm.n = n_names;
+    for (uint32_t q = 0; q < n_names; q++) {
+        nm.len[q] = name_len[q];
+        memcpy(nm.w[q], names + (size_t)BRX_MEMBER_MAX_NAME * q, name_len[q]);
+        for (uint32_t p = 0; p < q; p++)
+            if (nm.len[p] == nm.len[q] && !memcmp(nm.w[p], nm.w[q], sizeof nm.w[q])) return refuse(call, "a name stands twice in names");
+    }
+    const int given = (line_off != nullptr) + (sel_stream != nullptr) + (sel_rec != nullptr) + (kind != nullptr);
+    if (given != 0 && given != 4) return refuse(call, "line_off, sel_stream, sel_rec and kind go together");
+    if (!given && line_flags) return refuse(call, "line_flags is given in count mode");
+    if (!given && !lines) return refuse(call, "lines is NULL in count mode");
+    if (n == 0) return BRX_SUCCESS;
+    if (!out_off || !len || !count || !pos_off) return refuse(call, "NULL table");
+    if ((!pos || !what) && n_pos > 0) return refuse(call, "pos or what is NULL with n_pos > 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return refuse(call, "span out of range");
+    // the grids and the scratch follow from n, n_pos and m alone: no count is read back
+    // (n_names * m needs no check of its own: m < 2^39 here and n_names <= 8, so every index q * m + j and the clears' byte counts fit)
+    if ((m + 255u) / 256u > 0x7fffffffull) return refuse(call, "m out of range");
+    if (n_pos > (uint64_t)1 << 40) return refuse(call, "n_pos out of range");
+    BrxMbArgs x;
+    x.a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, 1u, BRX_TAKE_NO_DELIM, nullptr, nullptr, m);
+    x.what = what; x.lines = lines; x.line_off = line_off; x.m = m;
+    x.sel_stream = sel_stream; x.sel_rec = sel_rec; x.kind = kind; x.line_flags = line_flags;
+    x.max_tiles = brx_mb_max_tiles(n, n_pos);
+    x.pre = nullptr; x.slines = nullptr; x.sum = nullptr; x.in = nullptr;
+    const size_t tiles = (size_t)x.max_tiles;
+    return run_pass(c, hip_stream, c->member_ring, brx_mb_region_bytes(n, tiles),
+                    brx_mb_region_bytes((size_t)n + n / 4u + 1024u, tiles + tiles / 4u + 1024u), "member scratch allocation failed",
+                    [&](void *scratch, hipStream_t st) { brx_launch_member(x, nm, scratch, st); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 

@@ -288,5 +288,19 @@ inline void unescape_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out
                            escape, text_len, status, dst_off, dst, total, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_unescape_batch: ") + brx_last_error());
 }
+// The named members of the JSON Lines objects of a batch as selections for the calls above: count, pos_off, pos, what and n_pos as a
+// fill-mode brx_index_set_batch call with the delimiters { } [ ] : , and the line feed left them; names (host memory) holds name q at
+// names[32 q .. 32 q + name_len[q]).  Count mode (line_off, sel_stream, sel_rec, kind nullptr): lines[i].  Fill mode: entry (q, j) at
+// q * m + j is the last depth-1 member of line j whose key is name q: sel_stream / sel_rec as the record calls take them, kind
+// BRX_MEMBER_MISSING ... BRX_MEMBER_BAD; line_flags[j] (may be nullptr) BRX_MEMBER_LONG_KEY | _ESCAPED_KEY | _UNBALANCED.
+inline void member_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                         const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                         const uint8_t *names, const uint32_t *name_len, uint32_t n_names, uint64_t *lines, const uint64_t *line_off = nullptr,
+                         uint64_t m = 0, uint32_t *sel_stream = nullptr, uint64_t *sel_rec = nullptr, uint8_t *kind = nullptr,
+                         uint8_t *line_flags = nullptr, void *stream = nullptr) {
+    if (brx_member_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, what, n_pos, names, name_len, n_names, lines, line_off, m,
+                         sel_stream, sel_rec, kind, line_flags, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_member_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

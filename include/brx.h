@@ -922,6 +922,93 @@ int brx_unescape_batch(brx_ctx *ctx,
                        const uint64_t *dst_off, uint8_t *dst, uint64_t total,
                        void *hip_stream);
 
+/* ---- named members of JSON Lines objects as selections for the record calls (device memory only) -----------------
+ * The record calls above take (sel_stream, sel_rec) pairs.  For JSON Lines nobody can say on the device which record holds the value
+ * of "text" in line 17: keys come in any order, some are missing, values may be objects and arrays, a name may repeat inside a nested
+ * value, a key may be duplicated.  This pass is the verb in front of the record calls: from `what` it emits, per line and per
+ * requested name, the pair that the record calls take as they are, and the kind of value that stands there.
+ * out, out_off, len, n and span are exactly as for brx_take_batch.  count, pos_off, pos, what and n_pos are what a fill-mode
+ * brx_index_set_batch call left behind, with quote '"', escape '\' and a delimiter set that contains { } [ ] : , and the line feed;
+ * pos_off is the exclusive prefix sum of count.
+ *   names, name_len   HOST memory, whatever the other pointers are, read before the call returns.  Name q is names[32 q .. 32 q +
+ *             name_len[q]); 1 <= n_names <= BRX_MEMBER_MAX_NAMES = 8, 1 <= name_len[q] <= BRX_MEMBER_MAX_NAME = 32, no name twice.  They
+ *             travel to the kernels as launch arguments (8 x 32 = 256 bytes), as find's needle does: no upload, and the call stays
+ *             enqueue-only.
+ * Everything else is DEVICE memory.
+ * THE RULE.  Boundary k of stream i is w_k = what[pos_off[i] + k], at P(i,k) with the clamps of brx_take_batch's RULE.  An index
+ * pos_off[i] + k >= n_pos is not loaded, neither from what nor from pos: such a boundary counts as a neutral byte.
+ *   LINES.  Line r of stream i holds the boundaries behind the r-th '\n' boundary, up to and including the (r + 1)-th.  Every stream
+ *       has lines[i] = (number of '\n' boundaries) + 1 lines; the last one is the TRAILING line, empty when the stream ends on a
+ *       line feed (take's convention for records).  Line r of stream i is entry j = line_off[i] + r.
+ *   DEPTH.  d(k) = the sum of +1 for every '{' or '[' and -1 for every '}' or ']' among the boundaries of the same line in front of
+ *       k.  It is signed and restarts at 0 behind every '\n' boundary: a malformed line cannot spoil the next.  Other bytes are neutral.
+ *   MEMBER.  A ':' boundary k with d(k) == 1.  Its KEY RECORD is record k of the stream under BRX_TAKE_NO_DELIM with D = 1, leading
+ *       and trailing 0x20, 0x09 and 0x0D dropped.  The member CARRIES name q iff what is left is '"', the bytes of name q, '"':
+ *       bytewise, no escape is resolved.  A key record longer than BRX_MEMBER_MAX_KEY = 64 bytes before trimming is not looked at and
+ *       matches nothing (parse's LONG).
+ *   VALUE of the member at k.  w_{k+1} in the same line and ',' or '}': SCALAR, the value is record k + 1.  '{': OBJECT.  '[': ARRAY
+ *       (for both, record k + 1 is the blank in front of the opener).  Anything else, or no further boundary in the line: BAD.  In
+ *       all four cases sel_rec = k + 1.
+ *   LAST WINS.  For entry (q, j) the LAST member of line j that carries name q wins, as json.loads has it with duplicates.  None:
+ *       kind = MISSING and sel_rec = UINT64_MAX, which by take's pairs-mode rule selects nothing.  sel_stream is i in every case.
+ *   Results are column-major: entry (q, j) is at index q * m + j, so one name's column is a contiguous selection for a record call.
+ *   line_flags[j] (optional): BRX_MEMBER_LONG_KEY: a depth-1 member of the line had a key record above 64 bytes.
+ *       BRX_MEMBER_ESCAPED_KEY: a depth-1 key record that was looked at contains 0x5C (it may spell a name with an escape).
+ *       BRX_MEMBER_UNBALANCED: the depth fell below 0 somewhere in the line, or is not 0 behind the line's last boundary other than
+ *       its '\n'.  A line with flags 0 whose members are all SCALAR or MISSING is one the caller need not look at again.
+ * COUNT MODE (line_off, sel_stream, sel_rec and kind all NULL; lines required): lines[i] for i < n.
+ * FILL MODE (all four given; lines may be NULL, and if given it is written as in count mode): every slot (q, j) with j < m that belongs
+ * to a line is written, MISSING included; a line with j >= m is not written: m bounds the results as `total` bounds pos.  Nothing at
+ * index >= n_names * m is written; line_flags, when given, for j < m only.  While the call runs, sel_rec[0 .. n_names * m) and
+ * sel_stream[0 .. m) are the pass's own (cleared first, then raised); a slot j < m that is no stream's line (a line_off that is not
+ * the prefix sum of lines) comes out MISSING with sel_stream = n.
+ * Nothing at or beyond out + span, in front of out, outside a stream, or at or beyond what + n_pos or pos + n_pos is ever loaded.
+ * Stale or garbage pos, what or count give wrong members, never a load or a store outside these bounds.
+ * Check values, from the check stream of brx_index_set_batch (pos and what as printed there, count 15); stream between brackets, per
+ * line the names found as name KIND sel_rec, the others MISSING:
+ *   names a, b, c, open:
+ *   [{"a":"x,\"y:}","b":[1,2]}\n{"c":"\\"}\n{"open":"[\] line 0: a SCALAR 2 b ARRAY 4 flags 0; line 1: c SCALAR 11 flags 0; line 2: open BAD 15 flags 4
+ *   (lines = 3; record 11 is "\\")
+ *   [{"a":1,"a":2}] line 0: a SCALAR 4 flags 0
+ *   [{"user":{"text":1},"text":2}] line 0: text SCALAR 7 user OBJECT 2 flags 0
+ *   [{ "a"<09>:1}] line 0: a SCALAR 2 flags 0
+ *   [{<30 x 20>"<32 x k>":1}] line 0: k32 SCALAR 2 flags 0                    (a key record of 64 bytes; k32 = 32 x k)
+ *   [{<31 x 20>"<32 x k>":1}] line 0: none flags 1                            (... of 65)
+ *   [{"a":1}}] line 0: a SCALAR 2 flags 4
+ *   [}{"a":1}] line 0: none flags 4
+ *   [{"a\u0062":1}\n] line 0: none flags 2; line 1: none flags 0              (name ab)
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued, and behind a
+ * brx_index_set_batch call on the same stream it needs no synchronisation in between.  The context's lock is held to enqueue only.
+ * Scratch (tile prefix sums, lines per stream, two small records per tile of 4096 boundaries) belongs to the context and is sized from
+ * n and n_pos with no count read back; every launch has a region of its own (a ring of 16 of this pass's own).
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; names or name_len NULL; n_names 0 or above
+ * 8; a name_len of 0 or above 32; a name twice; only some of line_off / sel_stream / sel_rec / kind; line_flags in count mode; lines
+ * NULL in count mode; then n = 0 returns BRX_SUCCESS, no launch; then out_off, len, count or pos_off NULL; pos or what NULL with
+ * n_pos > 0; span, m or n_pos out of range of one launch (the bound on m keeps n_names * m in range too).
+ * Not in scope: paths into nested values, and the extent of a nested value; resolving escapes in keys; names longer than 32 bytes or
+ * more than 8 names; validating JSON; pretty-printed JSON with line feeds inside an object; any change to brx_index_set_batch or to
+ * the record calls.
+ * Count mode reads `what` once, fill mode twice, plus the key records of the depth-1 members; no reference counterpart. */
+#define BRX_MEMBER_MAX_NAMES 8u
+#define BRX_MEMBER_MAX_NAME  32u
+#define BRX_MEMBER_MAX_KEY   64u
+#define BRX_MEMBER_MISSING 0u /* no depth-1 member of the line carries the name; sel_rec = UINT64_MAX */
+#define BRX_MEMBER_SCALAR  1u /* the value is record sel_rec */
+#define BRX_MEMBER_OBJECT  2u /* a nested object starts behind record sel_rec */
+#define BRX_MEMBER_ARRAY   3u /* a nested array starts behind record sel_rec */
+#define BRX_MEMBER_BAD     4u /* something else follows the ':' */
+#define BRX_MEMBER_LONG_KEY    1u
+#define BRX_MEMBER_ESCAPED_KEY 2u
+#define BRX_MEMBER_UNBALANCED  4u
+int brx_member_batch(brx_ctx *ctx,
+                     const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                     const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                     const uint8_t *names, const uint32_t *name_len, uint32_t n_names,
+                     uint64_t *lines,
+                     const uint64_t *line_off, uint64_t m,
+                     uint32_t *sel_stream, uint64_t *sel_rec, uint8_t *kind, uint8_t *line_flags,
+                     void *hip_stream);
+
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
  * ANY queued stream decodes ALL streams queued on that context in one batch (N live Decompressors cost about one
