@@ -50,6 +50,8 @@ TEXT_OK, TEXT_BARE, TEXT_NULL, TEXT_BAD = 0, 1, 2, 3  # BRX_TEXT_OK ... (the sta
 MEMBER_MAX_NAMES, MEMBER_MAX_NAME, MEMBER_MAX_KEY = 8, 32, 64  # BRX_MEMBER_MAX_NAMES ... (brx_member_batch)
 MEMBER_MISSING, MEMBER_SCALAR, MEMBER_OBJECT, MEMBER_ARRAY, MEMBER_BAD = 0, 1, 2, 3, 4  # BRX_MEMBER_MISSING ... (the kind byte)
 MEMBER_LONG_KEY, MEMBER_ESCAPED_KEY, MEMBER_UNBALANCED = 1, 2, 4  # BRX_MEMBER_LONG_KEY ... (the bits of line_flags)
+ELEMENTS_OK, ELEMENTS_NONE, ELEMENTS_NOT_ARRAY, ELEMENTS_UNCLOSED, ELEMENTS_MISMATCH = 0, 1, 2, 3, 4  # BRX_ELEMENTS_OK ... (brx_elements_batch)
+ELEMENTS_MAX_BLANK = 64  # BRX_ELEMENTS_MAX_BLANK
 
 
 class BrxError(RuntimeError):
@@ -133,6 +135,8 @@ def load_library():
     L.brx_member_batch.restype = ctypes.c_int
     L.brx_member_batch.argtypes = [P, P, P, P, U32, U64, P, P, P, P, U64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), U32, P, P, U64,
                                    P, P, P, P, P]
+    L.brx_elements_batch.restype = ctypes.c_int
+    L.brx_elements_batch.argtypes = [P, P, P, P, U32, U64, P, P, P, P, U64, P, P, U64, P, P, P, P, U64, P, P, P, P]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -190,7 +194,7 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
                     "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch",
-                    "brx_parse_batch", "brx_parse_time_batch", "brx_unescape_batch", "brx_member_batch"]
+                    "brx_parse_batch", "brx_parse_time_batch", "brx_unescape_batch", "brx_member_batch", "brx_elements_batch"]
 # Exported names with a digit in them.  They are kept apart because tests/test_abi.py compares EXPORTED_SYMBOLS with the names it reads
 # from include/brx.h by the pattern brx_[a-z_]+, which such a name does not match; tests/test_parse_f64_abi.py holds this list to the
 # header and to the library.
@@ -871,6 +875,69 @@ class Context:
             self.member_batch_device(*head, None, line_off.data_ptr(), M, sel_stream.data_ptr(), sel_rec.data_ptr(), kind.data_ptr(),
                                      line_flags.data_ptr(), hip_stream=hs)
         return lines, line_off, sel_stream[:, :M], sel_rec[:, :M], kind[:, :M], line_flags[:M]
+
+    def elements_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, what_ptr, n_pos, sel_stream_ptr,
+                              sel_rec_ptr, m, n_elem_ptr, status_ptr=None, end_ptr=None, el_off_ptr=None, total=0, el_stream_ptr=None,
+                              el_rec_ptr=None, el_kind_ptr=None, hip_stream=None):
+        """brx_elements_batch on raw device pointers: the elements of the JSON arrays whose openers the pairs (sel_stream, sel_rec) name
+        (sel_rec = the boundary index of a '[', as member_batch_device gives it for MEMBER_ARRAY), under the positions count / pos_off /
+        pos / what of a fill-mode index_set_batch call with delims b'{}[]:,\\n'.  Count mode (el_off_ptr, el_stream_ptr, el_rec_ptr and
+        el_kind_ptr None): n_elem[j] (uint64), status[j] (uint8, ELEMENTS_OK ... ELEMENTS_MISMATCH, may be None) and end[j] (uint64,
+        the closer's boundary index, may be None).  Fill mode: element t of entry j at el_off[j] + t, where that is inside the entry's
+        room and below `total`: el_stream (uint32), el_rec (uint64) and el_kind (uint8, MEMBER_SCALAR ... MEMBER_BAD); n_elem_ptr may
+        be None.  Nothing at or beyond `total` is written."""
+        rc = self._lib.brx_elements_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, what_ptr, n_pos,
+                                          sel_stream_ptr, sel_rec_ptr, m, n_elem_ptr, status_ptr, end_ptr, el_off_ptr, total, el_stream_ptr,
+                                          el_rec_ptr, el_kind_ptr, hip_stream)
+        if rc != 0:
+            raise BrxError("brx_elements_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def elements_batch(self, out, out_off, out_len, count, pos_off, pos, what, sel_stream, sel_rec, stream=None):
+        """The elements of JSON arrays as a selection for the record calls, found on the device.  out, out_off, out_len and stream as
+        for index_batch; count, pos_off, pos, what as index_set_batch(delims=b'{}[]:,\\n') returned them; (sel_stream, sel_rec): the
+        openers, as one row of member_batch's sel_stream / sel_rec -- entries that are not MEMBER_ARRAY may stay in it.
+        Returns (n_elem, el_off, status, end, el_stream, el_rec, el_kind): per entry the number of elements (int64), its exclusive
+        prefix sum, the status (uint8: ELEMENTS_OK, ELEMENTS_NONE for MISSING, ELEMENTS_NOT_ARRAY, ELEMENTS_UNCLOSED, ELEMENTS_MISMATCH
+        for an array closed by '}') and the boundary index of the closer (int64, -1 for NONE and NOT_ARRAY); per element, E =
+        sum(n_elem) of them, element t of entry j at el_off[j] + t: el_stream (int32) and el_rec (int64), a pairs-mode selection for
+        the record calls, and el_kind (uint8): MEMBER_SCALAR (the record is the element), MEMBER_OBJECT, MEMBER_ARRAY (el_rec is again
+        an opener: a second elements_batch call takes the nested arrays), MEMBER_BAD.  `[]` and `[ ]` have 0 elements; `[1,]` has a
+        blank second one, which parse_batch reports as PARSE_EMPTY.  A count-mode call, a cumsum on the device, one scalar read back
+        (the total of elements), a fill-mode call.  The embedding matrix of a batch whose lines carry "emb":[...]:
+            count, _, pos_off, pos, what = ctx.index_set_batch(out, out_off, out_len, delims=b'{}[]:,\\n')
+            lines, line_off, ss, sr, kind, flags = ctx.member_batch(out, out_off, out_len, count, pos_off, pos, what, [b"emb"])
+            n_elem, el_off, status, end, el_stream, el_rec, el_kind = ctx.elements_batch(out, out_off, out_len, count, pos_off, pos, what,
+                                                                                         ss[0], sr[0])
+            val, st = ctx.parse_f64_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=el_stream, sel_rec=el_rec, spaces=True)
+            emb = val.view(M, D)  # where every n_elem is D"""
+        import torch
+        n, dev = int(out_len.numel()), out.device
+        hs = stream.cuda_stream if stream is not None else None
+        with _on(stream):
+            sel_stream = sel_stream.to(torch.int32).contiguous()
+            sel_rec = sel_rec.to(torch.int64).contiguous()
+            m = int(sel_stream.numel())
+            n_elem = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+            status = torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+            end = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+        head = (out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(), pos_off.data_ptr(),
+                pos.data_ptr() if pos.numel() else None, what.data_ptr() if what.numel() else None, int(pos.numel()),
+                sel_stream.data_ptr() if m else None, sel_rec.data_ptr() if m else None, m)
+        _rec_sync(out, stream)
+        self.elements_batch_device(*head, n_elem.data_ptr(), status.data_ptr(), end.data_ptr(), hip_stream=hs)
+        with _on(stream):
+            n_elem = n_elem[:m]
+            ends = torch.cumsum(n_elem, 0)
+            el_off = ends - n_elem
+            E = int(ends[-1].item()) if m else 0  # (the read-back: waits for the count pass)
+            el_stream = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+            el_rec = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
+            el_kind = torch.empty(max(E, 1), dtype=torch.uint8, device=dev)
+        if E > 0:
+            _rec_sync(out, stream)
+            self.elements_batch_device(*head, None, None, None, el_off.data_ptr(), E, el_stream.data_ptr(), el_rec.data_ptr(),
+                                       el_kind.data_ptr(), hip_stream=hs)
+        return n_elem, el_off, status[:m], end[:m], el_stream[:E], el_rec[:E], el_kind[:E]
 
     def parse_f64_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                                sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream=None):

@@ -40,6 +40,7 @@
 #include "brx_parse_time.h"
 #include "brx_unescape.h"
 #include "brx_member.h"
+#include "brx_elements.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -1737,6 +1738,39 @@ extern "C" int brx_member_batch(brx_ctx *c, const uint8_t *out, const uint64_t *
     return run_pass(c, hip_stream, c->member_ring, brx_mb_region_bytes(n, tiles),
                     brx_mb_region_bytes((size_t)n + n / 4u + 1024u, tiles + tiles / 4u + 1024u), "member scratch allocation failed",
                     [&](void *scratch, hipStream_t st) { brx_launch_member(x, nm, scratch, st); });
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- the elements of the JSON arrays behind a selection of openers, as a selection for the record calls (brx_elements.hip) ----
+extern "C" int brx_elements_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                                  const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                                  const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t *n_elem, uint8_t *status,
+                                  uint64_t *end, const uint64_t *el_off, uint64_t total, uint32_t *el_stream, uint64_t *el_rec, uint8_t *el_kind,
+                                  void *hip_stream) {
+    BRX_GUARD_BEGIN
+    const char *call = "brx_elements_batch";
+    static_assert(BRX_EL_OK == BRX_ELEMENTS_OK && BRX_EL_NONE == BRX_ELEMENTS_NONE && BRX_EL_NOT_ARRAY == BRX_ELEMENTS_NOT_ARRAY &&
+                  BRX_EL_UNCLOSED == BRX_ELEMENTS_UNCLOSED && BRX_EL_MISMATCH == BRX_ELEMENTS_MISMATCH &&
+                  BRX_EL_MAX_BLANK == BRX_ELEMENTS_MAX_BLANK, "the kernel's values are brx.h's");
+    if (!c) return refuse(call, "ctx is NULL");
+    if ((sel_stream == nullptr) != (sel_rec == nullptr)) return refuse(call, "sel_stream and sel_rec go together");
+    const int given = (el_off != nullptr) + (el_stream != nullptr) + (el_rec != nullptr) + (el_kind != nullptr);
+    if (given != 0 && given != 4) return refuse(call, "el_off, el_stream, el_rec and el_kind go together");
+    if (!given && !n_elem) return refuse(call, "n_elem is NULL in count mode");
+    if (m == 0) return BRX_SUCCESS;
+    if (!sel_stream) return refuse(call, "sel_stream and sel_rec are NULL");
+    if (n > 0 && (!out_off || !len || !count || !pos_off)) return refuse(call, "NULL table");
+    if ((!pos || !what) && n_pos > 0) return refuse(call, "pos or what is NULL with n_pos > 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return refuse(call, "span out of range");
+    // the grid follows from m alone; n_pos and total bound every index the kernel forms
+    if ((m + 255u) / 256u > 0x7fffffffull) return refuse(call, "m out of range");
+    if (n_pos > (uint64_t)1 << 40) return refuse(call, "n_pos out of range");
+    if (given && total > (uint64_t)1 << 40) return refuse(call, "total out of range");
+    BrxElArgs x;
+    x.a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, 1u, BRX_TAKE_NO_DELIM, sel_stream, sel_rec, m);
+    x.what = what; x.n_elem = n_elem; x.status = status; x.end = end;
+    x.el_off = el_off; x.total = total; x.el_stream = el_stream; x.el_rec = el_rec; x.el_kind = el_kind;
+    return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_elements(x, st); return launched(); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 

@@ -302,5 +302,19 @@ inline void member_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_o
                          sel_stream, sel_rec, kind, line_flags, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_member_batch: ") + brx_last_error());
 }
+// The elements of the JSON arrays whose openers (sel_stream, sel_rec) name -- a column of member_batch's output, sel_rec the boundary of
+// the '[' -- as a selection for the record calls.  Count mode (el_off, el_stream, el_rec, el_kind nullptr): n_elem[j], status[j]
+// (BRX_ELEMENTS_OK ... BRX_ELEMENTS_MISMATCH, may be nullptr) and end[j] (the closer's boundary, may be nullptr).  Fill mode: element t
+// of entry j at el_off[j] + t, inside the entry's room and below total: el_stream / el_rec as the record calls take them, el_kind
+// BRX_MEMBER_SCALAR ... BRX_MEMBER_BAD; n_elem may be nullptr.
+inline void elements_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                           const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                           const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, uint64_t *n_elem, uint8_t *status = nullptr,
+                           uint64_t *end = nullptr, const uint64_t *el_off = nullptr, uint64_t total = 0, uint32_t *el_stream = nullptr,
+                           uint64_t *el_rec = nullptr, uint8_t *el_kind = nullptr, void *stream = nullptr) {
+    if (brx_elements_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, what, n_pos, sel_stream, sel_rec, m, n_elem, status, end,
+                           el_off, total, el_stream, el_rec, el_kind, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_elements_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

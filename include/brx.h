@@ -985,7 +985,8 @@ int brx_unescape_batch(brx_ctx *ctx,
  * 8; a name_len of 0 or above 32; a name twice; only some of line_off / sel_stream / sel_rec / kind; line_flags in count mode; lines
  * NULL in count mode; then n = 0 returns BRX_SUCCESS, no launch; then out_off, len, count or pos_off NULL; pos or what NULL with
  * n_pos > 0; span, m or n_pos out of range of one launch (the bound on m keeps n_names * m in range too).
- * Not in scope: paths into nested values, and the extent of a nested value; resolving escapes in keys; names longer than 32 bytes or
+ * Not in scope: paths into nested values, and the extent of a nested value (of a nested array, with its elements: brx_elements_batch
+ * below); resolving escapes in keys; names longer than 32 bytes or
  * more than 8 names; validating JSON; pretty-printed JSON with line feeds inside an object; any change to brx_index_set_batch or to
  * the record calls.
  * Count mode reads `what` once, fill mode twice, plus the key records of the depth-1 members; no reference counterpart. */
@@ -1008,6 +1009,82 @@ int brx_member_batch(brx_ctx *ctx,
                      const uint64_t *line_off, uint64_t m,
                      uint32_t *sel_stream, uint64_t *sel_rec, uint8_t *kind, uint8_t *line_flags,
                      void *hip_stream);
+
+/* ---- the elements of JSON arrays as selections for the record calls (device memory only) -----------------------------
+ * brx_member_batch answers kind = BRX_MEMBER_ARRAY and sel_rec = the boundary of the '[' for "emb":[0.12,-3.4e-2,...], and there the
+ * pipeline ended.  This pass is the verb between member and the record calls: for a selection of array openers it gives the number of
+ * elements, the closing bracket (the extent of the nested value) and the (stream, record) pair and kind of every element.  The pairs
+ * are a selection that the record calls take as they stand: brx_parse_f64_batch over them is the embedding matrix.
+ * Everything is DEVICE memory.  out ... n_pos are exactly as for brx_member_batch: the tables of a fill-mode brx_index_set_batch call
+ * at { } [ ] : , and the line feed, quote '"', escape '\'.  (sel_stream, sel_rec) is a pairs-mode selection of m entries as
+ * brx_member_batch emits it: sel_rec = the boundary index of the opener.  A whole column of member's output may be passed, MISSING
+ * and SCALAR entries included.
+ * THE RULE.  Boundary k of stream i, w_k and C(i) = min(count[i], n_pos - pos_off[i]) (0 where pos_off[i] >= n_pos), the boundaries
+ * that count, are as in brx_member_batch's RULE.  Nothing at or behind n_pos is loaded, neither from what nor from pos.  Entry j has
+ * i = sel_stream[j], r = sel_rec[j].
+ *   BRX_ELEMENTS_NONE.  i >= n or r >= C(i): n_elem = 0, end = UINT64_MAX.  Member's MISSING (sel_rec = UINT64_MAX) lands here.
+ *   BRX_ELEMENTS_NOT_ARRAY.  w_r is not '[': n_elem = 0, end = UINT64_MAX.
+ *   THE WALK.  Otherwise k = r + 1, r + 2, ... with the relative depth e = 1 and the separator s = r.  '{' and '[' give e += 1.  '}'
+ *       and ']' give e -= 1; at e = 0 the array ends at k: status BRX_ELEMENTS_OK for ']', BRX_ELEMENTS_MISMATCH for '}', end = k, and
+ *       the last element ends here.  A ',' at e = 1 ends an element, then s = k.  Every other byte is neutral.  A '\n' boundary stops
+ *       the walk (BRX_ELEMENTS_UNCLOSED, end = k), as does k = C(i) (BRX_ELEMENTS_UNCLOSED, end = C(i)); the elements ended so far
+ *       stand, the partial one behind the last separator is not an element.
+ *   AN ELEMENT that begins behind separator s has el_rec = s + 1 and el_stream = i.  Its kind follows from w_{s+1}: ',' ']' '}':
+ *       BRX_MEMBER_SCALAR, the element is record s + 1 under BRX_TAKE_NO_DELIM with D = 1.  '{': BRX_MEMBER_OBJECT.  '[':
+ *       BRX_MEMBER_ARRAY, and el_rec is again an opener, so a second call takes nested arrays as they are.  ':' and anything else:
+ *       BRX_MEMBER_BAD.
+ *   EMPTY ARRAY.  [] and [1] look alike in what.  Where the closer stands at r + 1 and record r + 1 is at most
+ *       BRX_ELEMENTS_MAX_BLANK = 64 bytes and holds nothing but 0x20, 0x09 and 0x0D, n_elem = 0.  A record above 64 bytes is not
+ *       looked at and counts as one element (parse's LONG).
+ *   Consequences: [1,] and [,] have a blank SCALAR element, which brx_parse_batch reports as EMPTY.
+ * COUNT MODE (el_off, el_stream, el_rec and el_kind all NULL; n_elem required; status and end optional): n_elem[j], status[j] and
+ * end[j] for j < m.
+ * FILL MODE (all four given; n_elem, status and end optional, written as in count mode): element t of entry j goes to slot el_off[j] +
+ * t iff t is below the room of j and the slot is below total; the room of j is (j + 1 < m ? el_off[j + 1] : total) - el_off[j], 0 where
+ * that is negative.  Other slots are not touched; nothing at or beyond total is written.
+ * Nothing outside the bounds that brx_member_batch's contract names is ever loaded.  Stale or garbage tables give wrong elements,
+ * never a load or a store outside these bounds.
+ * Check values, r = 2 (the '[' of {"a":[ ) where not said otherwise; stream between brackets, then the status, n_elem, the elements
+ * as (el_rec KIND) and end:
+ *   [{"a":[]}] r 2: OK 0 end 3
+ *   [{"a":[ ]}] r 2: OK 0 end 3
+ *   [{"a":[1,]}] r 2: OK 2 (3 SCALAR)(4 SCALAR) end 4
+ *   [{"a":[1:2]}] r 2: OK 1 (3 BAD) end 4
+ *   [{"a":[1}] r 2: MISMATCH 1 (3 SCALAR) end 3
+ *   [{"a":[1,2\n] r 2: UNCLOSED 1 (3 SCALAR) end 4
+ *   [{"a":[1,[2] r 2: UNCLOSED 1 (3 SCALAR) end 5
+ *   [{"a":[[1,2],{"b":[3]},4]}] r 2: OK 3 (3 ARRAY)(7 OBJECT)(13 SCALAR) end 13
+ *   [{"a":["],[",2]}] r 2: OK 2 (3 SCALAR)(4 SCALAR) end 4
+ *   [{"a":[<64 x 20>]}] r 2: OK 0 end 3
+ *   [{"a":[<65 x 20>]}] r 2: OK 1 (3 SCALAR) end 3
+ *   [{"a":[,]}] r 2: OK 2 (3 SCALAR)(4 SCALAR) end 4
+ *   [{"a":{}}] r 2: NOT_ARRAY 0
+ *   [{"a":[1]}] r 9: NONE 0
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued, and behind
+ * brx_index_set_batch and brx_member_batch calls on the same stream it needs no synchronisation in between.  The context's lock is
+ * held to enqueue only.  One launch, no scratch of the context's.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; only one of sel_stream / sel_rec; only some
+ * of el_off / el_stream / el_rec / el_kind; n_elem NULL in count mode; then m = 0 returns BRX_SUCCESS, no launch; then sel_stream
+ * NULL; out_off, len, count or pos_off NULL with n > 0; pos or what NULL with n_pos > 0; span, m, n_pos or total out of range of one
+ * launch.
+ * Not in scope: objects ('{' gives NOT_ARRAY: the members of a nested object are the next verb); paths; validating JSON;
+ * pretty-printed JSON with line feeds inside an array; any change to brx_index_set_batch, brx_member_batch or the record calls.
+ * Reads `what` behind every opener up to its stop, once per call, and record r + 1 of the arrays whose closer stands at r + 1; no
+ * reference counterpart.  An array that has not ended 64 boundaries behind its opener is taken by its whole wavefront, 1024
+ * boundaries per step. */
+#define BRX_ELEMENTS_MAX_BLANK 64u
+#define BRX_ELEMENTS_OK        0u /* the array ended at a ']' */
+#define BRX_ELEMENTS_NONE      1u /* the entry selects no boundary that counts */
+#define BRX_ELEMENTS_NOT_ARRAY 2u /* the boundary is not a '[' */
+#define BRX_ELEMENTS_UNCLOSED  3u /* a line feed or the stream's end came first */
+#define BRX_ELEMENTS_MISMATCH  4u /* the array ended at a '}' */
+int brx_elements_batch(brx_ctx *ctx,
+                       const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                       const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                       const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                       uint64_t *n_elem, uint8_t *status, uint64_t *end,
+                       const uint64_t *el_off, uint64_t total, uint32_t *el_stream, uint64_t *el_rec, uint8_t *el_kind,
+                       void *hip_stream);
 
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
