@@ -282,6 +282,32 @@ def _rec_gather(out, stream, m, length, stride, fill_pass):
     return dst[:total], dst_off
 
 
+# ---- what the wrappers of the boundary calls share (index, index_quoted, index_escaped, index_set, find: DESIGN.md 11.1) --------------
+def _two_pass(device, args, out, out_len, stream, positions, has_open=False, has_what=False):
+    """Count mode, then fill mode, of `device`, the pass's *_batch_device method: behind its own leading arguments `args` it takes
+    count_ptr, open_ptr (only with has_open), pos_off_ptr, pos_ptr, what_ptr (only with has_what), total and hip_stream.  Returns count,
+    or (count, open) with has_open; with `positions` (count[, open], pos_off, pos[, what]): the grand total is read back to allocate
+    `pos` (and `what`)."""
+    import torch
+    n = int(out_len.numel())
+    count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass clears it, or writes every entry)
+    head = (count, torch.empty(max(n, 1), dtype=torch.int32, device=out.device)[:n]) if has_open else (count,)
+    hs = stream.cuda_stream if stream is not None else None
+    _rec_sync(out, stream)
+    device(*args, *(t.data_ptr() for t in head), hip_stream=hs)
+    if not positions:
+        return head if has_open else count
+    with _on(stream):
+        ends = torch.cumsum(count, 0)
+        pos_off = ends - count
+        total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
+        tail = (torch.empty(max(total, 1), dtype=torch.int64, device=out.device),)
+        if has_what:
+            tail += (torch.empty(max(total, 1), dtype=torch.uint8, device=out.device),)
+    device(*args, *(None for _ in head), pos_off.data_ptr(), *(t.data_ptr() for t in tail), total, hip_stream=hs)
+    return head + (pos_off,) + tuple(t[:total] for t in tail)
+
+
 class Context:
     """One brx_ctx: a GPU, its tables, scratch and stream.  `options`: {name: value} of OPTIONS, applied at creation."""
 
@@ -447,23 +473,8 @@ class Context:
         in stream i, pos[pos_off[i] + k] the offset within stream i of the k-th -- or `count` alone with positions=False.  stream: a
         torch.cuda.Stream the work is enqueued on; None = the context's own stream.  With positions the call reads the grand total
         back to allocate `pos`: the one synchronisation a caller that wants the positions cannot avoid."""
-        import torch
-        n = int(out_len.numel())
-        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass clears it itself)
-        hs = stream.cuda_stream if stream is not None else None
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        args = (int(delim), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
-        self.index_batch_device(*args, count.data_ptr(), hip_stream=hs)
-        if not positions:
-            return count
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            ends = torch.cumsum(count, 0)
-            pos_off = ends - count
-            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
-            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
-        self.index_batch_device(*args, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
-        return count, pos_off, pos[:total]
+        args = (int(delim), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), int(out_len.numel()), int(out.numel()))
+        return _two_pass(self.index_batch_device, args, out, out_len, stream, positions)
 
     def index_quoted_batch_device(self, delim, quote, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, open_ptr=None, pos_off_ptr=None,
                                   pos_ptr=None, total=0, hip_stream=None):
@@ -482,24 +493,8 @@ class Context:
         (count, open, pos_off, pos): count, pos_off and pos as index_batch gives them (int64 device tensors), open an int32 device
         tensor, 1 where stream i ends inside a quoted field -- or (count, open) with positions=False.  With positions the call reads
         the grand total back to allocate `pos`, as index_batch does."""
-        import torch
-        n = int(out_len.numel())
-        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass writes every entry)
-        open_ = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)[:n]
-        hs = stream.cuda_stream if stream is not None else None
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        args = (int(delim), int(quote), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
-        self.index_quoted_batch_device(*args, count.data_ptr(), open_.data_ptr(), hip_stream=hs)
-        if not positions:
-            return count, open_
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            ends = torch.cumsum(count, 0)
-            pos_off = ends - count
-            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
-            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
-        self.index_quoted_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
-        return count, open_, pos_off, pos[:total]
+        args = (int(delim), int(quote), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), int(out_len.numel()), int(out.numel()))
+        return _two_pass(self.index_quoted_batch_device, args, out, out_len, stream, positions, has_open=True)
 
     def index_escaped_batch_device(self, delim, quote, escape, flags, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, open_ptr=None,
                                    pos_off_ptr=None, pos_ptr=None, total=0, hip_stream=None):
@@ -521,25 +516,9 @@ class Context:
         pos) or (count, open) with positions=False; open has two bits: 1 = stream i ends inside a quoted field, 2 = it ends on an
         escape that has nothing to escape.  With positions the call reads the grand total back to allocate `pos`, as index_batch
         does."""
-        import torch
-        n = int(out_len.numel())
-        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass writes every entry)
-        open_ = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)[:n]
-        hs = stream.cuda_stream if stream is not None else None
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
         args = (int(delim), int(quote), int(escape), INDEX_NO_QUOTE if no_quote else 0, out.data_ptr(), out_off.data_ptr(),
-                out_len.data_ptr(), n, int(out.numel()))
-        self.index_escaped_batch_device(*args, count.data_ptr(), open_.data_ptr(), hip_stream=hs)
-        if not positions:
-            return count, open_
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            ends = torch.cumsum(count, 0)
-            pos_off = ends - count
-            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
-            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
-        self.index_escaped_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
-        return count, open_, pos_off, pos[:total]
+                out_len.data_ptr(), int(out_len.numel()), int(out.numel()))
+        return _two_pass(self.index_escaped_batch_device, args, out, out_len, stream, positions, has_open=True)
 
     def index_set_batch_device(self, delims, quote, escape, flags, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, open_ptr=None,
                                pos_off_ptr=None, pos_ptr=None, what_ptr=None, total=0, hip_stream=None):
@@ -561,26 +540,10 @@ class Context:
         pos_off, pos, what) -- what index_escaped_batch returns and `what`, a uint8 device tensor with the byte that stands at each
         position -- or (count, open) with positions=False.  With positions the call reads the grand total back to allocate `pos`
         and `what`, as index_batch does."""
-        import torch
-        n = int(out_len.numel())
-        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass writes every entry)
-        open_ = torch.empty(max(n, 1), dtype=torch.int32, device=out.device)[:n]
-        hs = stream.cuda_stream if stream is not None else None
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
         flags = (INDEX_NO_QUOTE if no_quote else 0) | (INDEX_NO_ESCAPE if no_escape else 0)
-        args = (bytes(delims), int(quote), int(escape), flags, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
-        self.index_set_batch_device(*args, count.data_ptr(), open_.data_ptr(), hip_stream=hs)
-        if not positions:
-            return count, open_
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            ends = torch.cumsum(count, 0)
-            pos_off = ends - count
-            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
-            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
-            what = torch.empty(max(total, 1), dtype=torch.uint8, device=out.device)
-        self.index_set_batch_device(*args, None, None, pos_off.data_ptr(), pos.data_ptr(), what.data_ptr(), total, hip_stream=hs)
-        return count, open_, pos_off, pos[:total], what[:total]
+        args = (bytes(delims), int(quote), int(escape), flags, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), int(out_len.numel()),
+                int(out.numel()))
+        return _two_pass(self.index_set_batch_device, args, out, out_len, stream, positions, has_open=True, has_what=True)
 
     def find_batch_device(self, needle, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr=None, pos_ptr=None, total=0,
                           hip_stream=None):
@@ -599,23 +562,8 @@ class Context:
         Returns (count, pos_off, pos), int64 device tensors: count[i] occurrences in stream i, pos[pos_off[i] + k] the offset within
         stream i of the first byte of the k-th -- or `count` alone with positions=False.  With positions the call reads the grand
         total back to allocate `pos`, as index_batch does."""
-        import torch
-        n = int(out_len.numel())
-        count = torch.empty(max(n, 1), dtype=torch.int64, device=out.device)[:n]  # (the pass clears it itself)
-        hs = stream.cuda_stream if stream is not None else None
-        if stream is None:
-            torch.cuda.current_stream(out.device).synchronize()  # (the context's stream is not ordered behind torch's)
-        args = (needle, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()))
-        self.find_batch_device(*args, count.data_ptr(), hip_stream=hs)
-        if not positions:
-            return count
-        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-            ends = torch.cumsum(count, 0)
-            pos_off = ends - count
-            total = int(ends[-1].item()) if n else 0  # (the read-back: waits for the count pass)
-            pos = torch.empty(max(total, 1), dtype=torch.int64, device=out.device)
-        self.find_batch_device(*args, None, pos_off.data_ptr(), pos.data_ptr(), total, hip_stream=hs)
-        return count, pos_off, pos[:total]
+        args = (needle, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), int(out_len.numel()), int(out.numel()))
+        return _two_pass(self.find_batch_device, args, out, out_len, stream, positions)
 
     def take_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                           sel_stream_ptr, sel_rec_ptr, m, rec_len_ptr, dst_off_ptr=None, dst_ptr=None, total=0, hip_stream=None):

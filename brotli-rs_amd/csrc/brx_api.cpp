@@ -1383,24 +1383,45 @@ extern "C" int brx_digest_batch(brx_ctx *c, uint32_t kind, const uint8_t *out, c
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
+static int refuse(const char *call, const char *what) { // "<call>: <what>", as brx_last_error() gives it
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", call, what);
+    return fail(BRX_ERR_INVALID_ARGUMENT, buf);
+}
+
+// ---- the boundary calls: where something stands in the decoded bytes of a batch (DESIGN.md 11.1, 12 .. 16) -------------------
+// What the five calls below share is defined once, here; a call states its name, its ctx check and its own checks, its ring, its
+// out-of-memory text and its launch.  Behind a call's own checks: the refusals that all five make, in their order (`what` is
+// brx_index_set_batch's, NULL for the others), the n == 0 exit, and one launch of the pass, `launch(scratch, max_tiles, workgroups,
+// stream)`, on a region of `ring` that `region_bytes` (the pass's brx_*_region_bytes) sizes.
+template <class F>
+static int boundary_pass(const char *call, brx_ctx *c, void *hip_stream, PassRing &ring, size_t (*region_bytes)(size_t, size_t),
+                         const char *oom, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, const uint64_t *count,
+                         const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, F launch) {
+    if ((pos_off == nullptr) != (pos == nullptr)) return refuse(call, "pos_off and pos go together");
+    if (what && !pos) return refuse(call, "what is given without pos");
+    if (!pos && !count) return refuse(call, "count is NULL in count mode");
+    if (n == 0) return BRX_SUCCESS;
+    if (!out_off || !len) return refuse(call, "NULL table");
+    // what the scratch of a launch must hold follows from n and span alone: no length is read back
+    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
+    if (max_tiles > (uint64_t)1 << 40) return refuse(call, "span out of range");
+    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
+    return run_pass(c, hip_stream, ring, region_bytes(n, (size_t)max_tiles),
+                    region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)), oom,
+                    [&](void *scratch, hipStream_t st) { launch(scratch, max_tiles, c->max_grid / 4u, st); });
+}
+
 // ---- record boundaries of the decoded streams of a batch (brx_index.hip) ----------------------------------------------------
 extern "C" int brx_index_batch(brx_ctx *c, uint8_t delim, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n,
                                uint64_t span, uint64_t *count, const uint64_t *pos_off, uint64_t *pos, uint64_t total,
                                void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: ctx is NULL");
-    if ((pos_off == nullptr) != (pos == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: pos_off and pos go together");
-    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: count is NULL in count mode");
-    if (n == 0) return BRX_SUCCESS;
-    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: NULL table");
-    // what the scratch of a launch must hold follows from n and span alone: no length is read back
-    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
-    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_batch: span out of range");
-    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
-    return run_pass(c, hip_stream, c->index_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
-                    brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                    "index scratch allocation failed", [&](void *scratch, hipStream_t st) {
-        brx_launch_index(out, out_off, len, n, span, delim, scratch, max_tiles, count, pos_off, pos, total, c->max_grid / 4u, st);
+    const char *call = "brx_index_batch";
+    if (!c) return refuse(call, "ctx is NULL");
+    return boundary_pass(call, c, hip_stream, c->index_ring, brx_ix_region_bytes, "index scratch allocation failed", out_off, len, n, span,
+                         count, pos_off, pos, nullptr, [&](void *scratch, uint64_t max_tiles, unsigned workgroups, hipStream_t st) {
+        brx_launch_index(out, out_off, len, n, span, delim, scratch, max_tiles, count, pos_off, pos, total, workgroups, st);
     });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
@@ -1410,22 +1431,14 @@ extern "C" int brx_index_quoted_batch(brx_ctx *c, uint8_t delim, uint8_t quote, 
                                       const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count, uint32_t *open,
                                       const uint64_t *pos_off, uint64_t *pos, uint64_t total, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_quoted_batch: ctx is NULL");
-    if (delim == quote) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_quoted_batch: delim and quote are the same byte");
-    if ((pos_off == nullptr) != (pos == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_quoted_batch: pos_off and pos go together");
-    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_quoted_batch: count is NULL in count mode");
-    if (n == 0) return BRX_SUCCESS;
-    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_quoted_batch: NULL table");
-    // what the scratch of a launch must hold follows from n and span alone: no length is read back
-    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
-    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_quoted_batch: span out of range");
-    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
-    return run_pass(c, hip_stream, c->index_quoted_ring, brx_iq_region_bytes(n, (size_t)max_tiles),
-                    brx_iq_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                    "quoted index scratch allocation failed", [&](void *scratch, hipStream_t st) {
-        brx_launch_index_quoted(out, out_off, len, n, span, delim, quote, scratch, max_tiles, count, open, pos_off, pos, total,
-                                c->max_grid / 4u, st);
+    const char *call = "brx_index_quoted_batch";
+    if (!c) return refuse(call, "ctx is NULL");
+    if (delim == quote) return refuse(call, "delim and quote are the same byte");
+    return boundary_pass(call, c, hip_stream, c->index_quoted_ring, brx_iq_region_bytes, "quoted index scratch allocation failed", out_off,
+                         len, n, span, count, pos_off, pos, nullptr,
+                         [&](void *scratch, uint64_t max_tiles, unsigned workgroups, hipStream_t st) {
+        brx_launch_index_quoted(out, out_off, len, n, span, delim, quote, scratch, max_tiles, count, open, pos_off, pos, total, workgroups,
+                                st);
     });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
@@ -1435,27 +1448,17 @@ extern "C" int brx_index_escaped_batch(brx_ctx *c, uint8_t delim, uint8_t quote,
                                        const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count,
                                        uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint64_t total, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: ctx is NULL");
-    if (flags & ~BRX_INDEX_NO_QUOTE) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: unknown flag bits");
-    if (delim == escape) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: delim and escape are the same byte");
-    if (!(flags & BRX_INDEX_NO_QUOTE) && quote == delim)
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: delim and quote are the same byte");
-    if (!(flags & BRX_INDEX_NO_QUOTE) && quote == escape)
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: quote and escape are the same byte");
-    if ((pos_off == nullptr) != (pos == nullptr))
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: pos_off and pos go together");
-    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: count is NULL in count mode");
-    if (n == 0) return BRX_SUCCESS;
-    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: NULL table");
-    // what the scratch of a launch must hold follows from n and span alone: no length is read back
-    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
-    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_escaped_batch: span out of range");
-    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
-    return run_pass(c, hip_stream, c->index_escaped_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
-                    brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                    "escaped index scratch allocation failed", [&](void *scratch, hipStream_t st) {
+    const char *call = "brx_index_escaped_batch";
+    if (!c) return refuse(call, "ctx is NULL");
+    if (flags & ~BRX_INDEX_NO_QUOTE) return refuse(call, "unknown flag bits");
+    if (delim == escape) return refuse(call, "delim and escape are the same byte");
+    if (!(flags & BRX_INDEX_NO_QUOTE) && quote == delim) return refuse(call, "delim and quote are the same byte");
+    if (!(flags & BRX_INDEX_NO_QUOTE) && quote == escape) return refuse(call, "quote and escape are the same byte");
+    return boundary_pass(call, c, hip_stream, c->index_escaped_ring, brx_ie_region_bytes, "escaped index scratch allocation failed",
+                         out_off, len, n, span, count, pos_off, pos, nullptr,
+                         [&](void *scratch, uint64_t max_tiles, unsigned workgroups, hipStream_t st) {
         brx_launch_index_escaped(out, out_off, len, n, span, delim, quote, escape, flags, scratch, max_tiles, count, open, pos_off, pos,
-                                 total, c->max_grid / 4u, st);
+                                 total, workgroups, st);
     });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
@@ -1466,40 +1469,29 @@ extern "C" int brx_index_set_batch(brx_ctx *c, const uint8_t *delims, uint32_t n
                                    uint64_t *count, uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint8_t *what,
                                    uint64_t total, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: ctx is NULL");
-    if (flags & ~(BRX_INDEX_NO_QUOTE | BRX_INDEX_NO_ESCAPE)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: unknown flag bits");
-    if (!delims) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: delims is NULL");
-    if (n_delims == 0 || n_delims > BRX_INDEX_SET_MAX)
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: n_delims must be 1 .. 8 (delims)");
+    const char *call = "brx_index_set_batch";
+    if (!c) return refuse(call, "ctx is NULL");
+    if (flags & ~(BRX_INDEX_NO_QUOTE | BRX_INDEX_NO_ESCAPE)) return refuse(call, "unknown flag bits");
+    if (!delims) return refuse(call, "delims is NULL");
+    if (n_delims == 0 || n_delims > BRX_INDEX_SET_MAX) return refuse(call, "n_delims must be 1 .. 8 (delims)");
     // the set as the kernels take it: byte k of one 64-bit launch argument (read here: the caller may reuse `delims` at once)
     uint64_t set = 0;
     for (uint32_t k = 0; k < n_delims; k++) {
         for (uint32_t j = 0; j < k; j++)
-            if (delims[j] == delims[k]) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: a byte stands twice in delims");
+            if (delims[j] == delims[k]) return refuse(call, "a byte stands twice in delims");
         set |= (uint64_t)delims[k] << (8u * k);
     }
     static_assert(BRX_INDEX_SET_NO_QUOTE == BRX_INDEX_NO_QUOTE && BRX_INDEX_SET_NO_ESCAPE == BRX_INDEX_NO_ESCAPE, "the kernels' flags are brx.h's");
     const bool quotes = !(flags & BRX_INDEX_NO_QUOTE), escapes = !(flags & BRX_INDEX_NO_ESCAPE);
     for (uint32_t k = 0; escapes && k < n_delims; k++)
-        if (delims[k] == escape) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: escape is one of delims");
+        if (delims[k] == escape) return refuse(call, "escape is one of delims");
     for (uint32_t k = 0; quotes && k < n_delims; k++)
-        if (delims[k] == quote) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: quote is one of delims");
-    if (quotes && escapes && quote == escape)
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: quote and escape are the same byte");
-    if ((pos_off == nullptr) != (pos == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: pos_off and pos go together");
-    if (what && !pos) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: what is given without pos");
-    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: count is NULL in count mode");
-    if (n == 0) return BRX_SUCCESS;
-    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: NULL table");
-    // what the scratch of a launch must hold follows from n and span alone: no length is read back
-    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
-    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_index_set_batch: span out of range");
-    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU)
-    return run_pass(c, hip_stream, c->index_set_ring, brx_ie_region_bytes(n, (size_t)max_tiles),
-                    brx_ie_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                    "set index scratch allocation failed", [&](void *scratch, hipStream_t st) {
-        brx_launch_index_set(out, out_off, len, n, span, set, n_delims, quote, escape, flags, scratch, max_tiles, count, open, pos_off,
-                             pos, what, total, c->max_grid / 4u, st);
+        if (delims[k] == quote) return refuse(call, "quote is one of delims");
+    if (quotes && escapes && quote == escape) return refuse(call, "quote and escape are the same byte");
+    return boundary_pass(call, c, hip_stream, c->index_set_ring, brx_ie_region_bytes, "set index scratch allocation failed", out_off, len,
+                         n, span, count, pos_off, pos, what, [&](void *scratch, uint64_t max_tiles, unsigned workgroups, hipStream_t st) {
+        brx_launch_index_set(out, out_off, len, n, span, set, n_delims, quote, escape, flags, scratch, max_tiles, count, open, pos_off, pos,
+                             what, total, workgroups, st);
     });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
@@ -1509,36 +1501,20 @@ extern "C" int brx_find_batch(brx_ctx *c, const uint8_t *needle, uint32_t needle
                               const uint64_t *len, uint32_t n, uint64_t span, uint64_t *count, const uint64_t *pos_off, uint64_t *pos,
                               uint64_t total, void *hip_stream) {
     BRX_GUARD_BEGIN
-    if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: ctx is NULL");
-    if (!needle) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: needle is NULL");
-    if (needle_len == 0 || needle_len > BRX_FIND_MAX_NEEDLE)
-        return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: needle_len is not 1 .. 16");
-    if ((pos_off == nullptr) != (pos == nullptr)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: pos_off and pos go together");
-    if (!pos && !count) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: count is NULL in count mode");
-    if (n == 0) return BRX_SUCCESS;
-    if (!out_off || !len) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: NULL table");
-    // what the scratch of a launch must hold follows from n and span alone: no length is read back
-    const uint64_t max_tiles = brx_ix_max_tiles(n, span);
-    if (max_tiles > (uint64_t)1 << 40) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_find_batch: span out of range");
-    // 4 workgroups of 8 waves per CU: all 32 wave slots of a CU (max_grid = 16 per CU).  The needle's bytes are read here, into
-    // the launch arguments: the caller may reuse its buffer when the call returns.
-    return run_pass(c, hip_stream, c->find_ring, brx_ix_region_bytes(n, (size_t)max_tiles),
-                    brx_ix_region_bytes((size_t)n + n / 4u + 1024u, (size_t)(max_tiles + max_tiles / 4u + 1024u)),
-                    "find scratch allocation failed", [&](void *scratch, hipStream_t st) {
-        brx_launch_find(out, out_off, len, n, span, needle, needle_len, scratch, max_tiles, count, pos_off, pos, total, c->max_grid / 4u,
-                        st);
+    const char *call = "brx_find_batch";
+    if (!c) return refuse(call, "ctx is NULL");
+    if (!needle) return refuse(call, "needle is NULL");
+    if (needle_len == 0 || needle_len > BRX_FIND_MAX_NEEDLE) return refuse(call, "needle_len is not 1 .. 16");
+    // The needle's bytes are read during the launch call, into the launch arguments: the caller may reuse its buffer when the call returns.
+    return boundary_pass(call, c, hip_stream, c->find_ring, brx_ix_region_bytes, "find scratch allocation failed", out_off, len, n, span,
+                         count, pos_off, pos, nullptr, [&](void *scratch, uint64_t max_tiles, unsigned workgroups, hipStream_t st) {
+        brx_launch_find(out, out_off, len, n, span, needle, needle_len, scratch, max_tiles, count, pos_off, pos, total, workgroups, st);
     });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 
 // ---- the record calls: entry j of a selection, under the positions of an index pass, with take's flags -----
 // What the six calls below share is defined once, here; a call states its name, its own flag bits, its own checks and its launch.
-static int refuse(const char *call, const char *what) { // "<call>: <what>", as brx_last_error() gives it
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", call, what);
-    return fail(BRX_ERR_INVALID_ARGUMENT, buf);
-}
-
 // everything the rule reads, as the call got it
 static BrxTakeArgs rec_args(const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
                             const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, uint64_t n_pos, uint32_t delim_len,

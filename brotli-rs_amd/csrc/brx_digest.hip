@@ -1,6 +1,7 @@
 // brx_digest.hip -- brx_digest_batch: CRC-32 / CRC-32C of every decoded stream of a batch, on the device (algebra: brx_digest.h).
 //
-// Three launches on the caller's stream, in the shape of the tile pass (brx_tiles.h: tiling, plan, ticket counter, item search):
+// Three launches on the caller's stream, in the shape of the tile pass (brx_tiles.h: tiling, plan, the wave's walk over the items,
+// item search):
 //   plan   brx_tiles.hip, with one accumulator word per stream cleared.
 //   tiles  the pass over the bytes.  Every lane keeps the raw CRC of ITS column of the rows (the rows flush_range wrote): 16 LDS lookups
 //          for the chunk, 4 to move the register on by one row.  Head and tail are masked; the chunk that holds the stream's last byte is
@@ -72,16 +73,13 @@ __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_digest_tiles_kernel(const ui
     if ((uint64_t)blockIdx.x * waves_per_wg >= total) return; // (the whole workgroup: nothing for any of its waves, not even a first item)
     for (uint32_t i = threadIdx.x; i < BRX_DG_LDS_WORDS; i += BRX_TP_WG) lds[i] = tab[i];
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+    for (TpWalk w = tp_walk(total); w.item < w.total; tp_advance(w, ticket)) {
+        const TpItem it = tp_item(w.item, out, out_off, len, n, pre);
         const uint64_t a = it.a, e = it.e, t1 = it.t1; // t1: the reference point of the tile
         uint32_t s = 0, tail = 0;
         for (uint32_t r = 0; r < it.rows; r++) {
             const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
-            const uint64_t c = row + 16u * lane;
+            const uint64_t c = row + 16u * w.lane;
             if (row >= a && row + BRX_TP_ROW <= e) { // (uniform) a row inside the stream
                 s = dg_step(s, *(const uint4 *)(uintptr_t)c, lds);
             } else if (c < e) { // an edge row: lanes behind the stream's end stand still, lanes in front of its start read nothing
@@ -101,15 +99,14 @@ __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_digest_tiles_kernel(const ui
         }
         // where this lane's register stands: behind its chunk of the last row, or one row further up if that chunk reaches beyond
         // the stream's end -- and from there to the reference point (< 2048 bytes by construction)
-        const uint64_t cl = it.t0 + (uint64_t)(it.rows - 1u) * BRX_TP_ROW + 16u * lane;
+        const uint64_t cl = it.t0 + (uint64_t)(it.rows - 1u) * BRX_TP_ROW + 16u * w.lane;
         const uint64_t at = cl + 16u > e ? cl + 16u - BRX_TP_ROW : cl + 16u;
         uint32_t part = dg_mul(s, tab[BRX_DG_SMALLPOW + ((uint32_t)(t1 - at) & 2047u)], poly) ^ tail;
 #pragma unroll
         for (int k = 32; k >= 1; k >>= 1) part ^= (uint32_t)__shfl_xor((int)part, k);
         const uint64_t behind = e - t1; // bytes of the stream behind this tile (< 2^32: the per-stream limit)
         if (behind) part = dg_mul(part, dg_pow_bytes((uint32_t)behind, tab, poly), poly);
-        if (lane == 0u && part) atomicXor(&acc[it.si], part);
-        item = tp_next(ticket, grid_waves, total, lane);
+        if (w.lane == 0u && part) atomicXor(&acc[it.si], part);
     }
 }
 

@@ -1,13 +1,13 @@
 // brx_find.hip -- brx_find_batch: where a byte sequence of 1 .. 16 bytes (the needle) occurs in every decoded stream of a batch, on the
 // device (layout: brx_find.h).
 //
-// The pass is the tile pass of brx_index.hip -- plan, count, and in fill mode scan (brx_index_scan_kernel itself) and fill -- with a
-// row body that looks across the edges of lane chunks, rows and tiles.  An occurrence belongs to the lane chunk that holds its LAST
-// byte: everything else of it lies in that chunk or in the 16 bytes in front of it, which have been loaded already -- by the lane
-// below (one __shfl_up of the four dwords), by lane 63 of the row before (four wave-uniform dwords kept across the row loop), or, in a
-// tile's first row, by one extra 16-byte load in front of the tile.  The order by last byte is the order by first byte, and the
-// position reported is the last byte's minus (m - 1).  A row's chain (load, shuffle, match) is longer than the plain pass's, so both
-// kernels issue the load of row r + 1 before they match row r.
+// The pass is the tile pass (brx_tiles.h) as brx_index.hip runs it -- plan, count, and in fill mode scan (brx_index_scan_kernel itself)
+// and fill -- with a row body that looks across the edges of lane chunks, rows and tiles.  An occurrence belongs to the lane chunk
+// that holds its LAST byte: everything else of it lies in that chunk or in the 16 bytes in front of it, which have been loaded
+// already -- by the lane below (one __shfl_up of the four dwords), by lane 63 of the row before (four wave-uniform dwords kept across
+// the row loop), or, in a tile's first row, by one extra 16-byte load in front of the tile.  The order by last byte is the order by
+// first byte, and the position reported is the last byte's minus (m - 1).  A row's chain (load, shuffle, match) is longer than the
+// plain pass's, so both kernels issue the load of row r + 1 before they match row r.
 // A byte outside the stream is replaced by ix_chunk with a value that occurs nowhere in the needle, so a window that reaches in front
 // of the stream or behind it mismatches whatever needle position falls there.
 // Ordering between tiles comes from the kernel boundaries alone: no wave ever waits for a value that another wave of the same launch
@@ -88,35 +88,32 @@ __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_find_count_kernel(const uint
                                                                       const uint64_t *__restrict__ pre, uint64_t max_tiles,
                                                                       uint64_t *__restrict__ tile_cnt, uint64_t *count,
                                                                       unsigned long long *ticket) {
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles; // (more tiles than `span` allows: a caller's error, nothing is written for them)
-    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
     const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+    for (TpWalk w = tp_walk(tp_total(pre, n, max_tiles)); w.item < w.total; tp_advance(w, ticket)) {
+        const TpItem it = tp_item(w.item, out, out_off, len, n, pre);
         uint4 carry = fd_halo(out, it.t0, it.a, it.e, arena0, arena1, f4);
         uint32_t acc = 0;
-        uint4 nx = ix_chunk(out, it.t0, lane, it.a, it.e, arena0, arena1, f4);
+        uint4 nx = ix_chunk(out, it.t0, w.lane, it.a, it.e, arena0, arena1, f4);
         for (uint32_t r = 0; r < it.rows; r++) {
             const uint4 v = nx; // (the next row's load is in flight while this row is matched)
-            if (r + 1u < it.rows) nx = ix_chunk(out, it.t0 + (uint64_t)(r + 1u) * BRX_TP_ROW, lane, it.a, it.e, arena0, arena1, f4);
-            const uint4 p = fd_prev(v, carry, lane);
+            if (r + 1u < it.rows) nx = ix_chunk(out, it.t0 + (uint64_t)(r + 1u) * BRX_TP_ROW, w.lane, it.a, it.e, arena0, arena1, f4);
+            const uint4 p = fd_prev(v, carry, w.lane);
             uint32_t f[4];
             fd_ends(p, v, rn, m, f);
             acc += __popc(f[0]) + __popc(f[1]) + __popc(f[2]) + __popc(f[3]);
         }
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) acc += (uint32_t)__shfl_xor((int)acc, k);
-        if (lane == 0u) {
-            if (tile_cnt) tile_cnt[item] = acc;
+        acc = tp_wave_sum(acc);
+        if (w.lane == 0u) {
+            if (tile_cnt) tile_cnt[w.item] = acc;
             if (count && acc) atomicAdd((unsigned long long *)&count[it.si], (unsigned long long)acc);
         }
-        item = tp_next(ticket, grid_waves, total, lane);
     }
 }
 
+// This kernel keeps the walk, the mask and the row emit in its own text: they are tp_walk / tp_advance, ix_mask and tp_emit_row
+// (brx_tiles.h, brx_index.h) letter for letter.  It holds 16 needle bytes next to the walk's scalars and spills about 30 of them, and
+// with the shared functions in it the compiler spills differently and find's fill lines of the rate tool come out up to 0.4 % above
+// the range of the text below (profiles/r24_boundary_passes.txt).  A change to one of the three goes here too.
 __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_find_fill_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
                                                                      const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
                                                                      uint4 rn, uint32_t m, uint32_t f4,

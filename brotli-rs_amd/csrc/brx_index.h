@@ -1,5 +1,5 @@
 // brx_index.h -- shared by brx_index.hip (kernels) and brx_api.cpp (brx_index_batch): the pass's part of one launch's scratch region;
-// and, for the kernels of brx_index.hip, brx_index_quoted.hip and brx_find.hip, how a row is loaded and matched.
+// and, for the kernels of brx_index.hip, brx_index_quoted.hip, brx_index_escaped.hip and brx_find.hip, how a row is loaded and matched.
 #pragma once
 #include <stdint.h>
 
@@ -21,7 +21,7 @@ void brx_launch_index(const void *out, const uint64_t *out_off, const uint64_t *
 // brx_index.hip, one workgroup of 1024: tile_cnt[0 .. tiles of the batch) -> its exclusive prefix sum, in place (also launched by brx_find.hip)
 __global__ void brx_index_scan_kernel(uint32_t n, const uint64_t *__restrict__ pre, uint64_t max_tiles, uint64_t *__restrict__ tile_cnt);
 
-// ---- what a row is matched with, shared by brx_index.hip, brx_index_quoted.hip and brx_find.hip ----
+// ---- what a row is matched with, shared by brx_index.hip, brx_index_quoted.hip, brx_index_escaped.hip and brx_find.hip ----
 // 0x80 in every byte of w that equals the delimiter (d4 = the delimiter in all four bytes).  x = w ^ d4 has a zero byte there; the sum
 // of a byte's low seven bits and 0x7F carries into bit 7 exactly when they are not all zero and never into the next byte, so the test
 // is exact for every byte value, 0x00, 0x80 and 0xFF included.
@@ -38,12 +38,34 @@ __device__ __forceinline__ uint32_t ix_nib(uint32_t m) {
     return t & 15u;
 }
 
+// bit k: byte k of the chunk equals the byte b4 holds four times
+__device__ __forceinline__ uint32_t ix_mask(uint4 v, uint32_t b4) {
+    return ix_nib(ix_eq(v.x, b4)) | (ix_nib(ix_eq(v.y, b4)) << 4) | (ix_nib(ix_eq(v.z, b4)) << 8) | (ix_nib(ix_eq(v.w, b4)) << 12);
+}
+
+// The first byte value that is none of these, four times: none of the nd (0 .. 8) bytes of `set` (byte k for k < nd), not `quote` if
+// `quotes`, not `escape` if `escapes`.  It is what ix_chunk puts where the stream is not: in front of a stream it ends any run and
+// toggles nothing, so the stream starts unescaped and outside quotes; behind it it changes no count.  At most 10 values are excluded,
+// so the walk ends at 10 or before.
+__device__ __forceinline__ uint32_t ix_filler(uint64_t set, uint32_t nd, uint32_t quote, uint32_t quotes, uint32_t escape,
+                                              uint32_t escapes) {
+    uint32_t f = 0u;
+    for (;;) {
+        bool hit = (quotes && f == quote) || (escapes && f == escape);
+        for (uint32_t k = 0; k < nd; k++) hit = hit || f == ((uint32_t)(set >> (8u * k)) & 0xFFu);
+        if (!hit) break;
+        f++;
+    }
+    return f * 0x01010101u;
+}
+
 // the low k bytes of a 64-bit word (k >= 8: all of it)
 __device__ __forceinline__ uint64_t ix_low_bytes(uint32_t k) { return k >= 8u ? ~0ull : (1ull << (8u * k)) - 1ull; }
 
-// The chunk of `lane` in the row at `row`, with every byte outside the stream [a, e) replaced by one that is not the delimiter (nd4 =
-// ~delimiter in all four bytes; brx_index_quoted.hip passes a byte that is neither its delimiter nor its quote).  Only aligned 16-byte chunks that hold a byte of the stream are loaded; of the (at most two) chunks
-// that reach over an end of the arena [arena0, arena1) only the stream's own bytes are, one by one.
+// The chunk of `lane` in the row at `row`, with every byte outside the stream [a, e) replaced by one that the pass reports nowhere
+// (nd4 in all four bytes: brx_index.hip passes ~delimiter, the others ix_filler or, brx_find.hip, a byte that is not in the needle).
+// Only aligned 16-byte chunks that hold a byte of the stream are loaded; of the (at most two) chunks that reach over an end of the
+// arena [arena0, arena1) only the stream's own bytes are, one by one.
 __device__ __forceinline__ uint4 ix_chunk(const uint8_t *out, uint64_t row, uint32_t lane, uint64_t a, uint64_t e, uint64_t arena0,
                                           uint64_t arena1, uint32_t nd4) {
     const uint64_t c = row + 16u * lane;

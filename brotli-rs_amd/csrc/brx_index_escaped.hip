@@ -14,26 +14,14 @@
 //   resolve  one workgroup, over all tiles of the batch in order: a scan with the composition of maps gives every tile the state it is
 //            entered in (a stream's first tile is a constant map: segmentation falls out of the composition); G = exclusive prefix sum
 //            of the counts selected by it; per stream count[i] as a difference of G and open[i] from the state behind its last tile.
-//   fill     the count kernel's row body from the tile's real entry state, then the fill of brx_index.hip on the selected mask.
+//   fill     the count kernel's row body from the tile's real entry state, then tp_emit_row (brx_tiles.h) on the selected mask.
+// brx_index_set_batch (a set of delimiters, the escape optional) is the same pass in a second dialect: see IeByte / IeSet below.
 // Ordering between tiles comes from the kernel boundaries alone: no wave ever waits for a value that another wave of the same launch
 // produces (no chained scan, no look-back), so there is nothing that could spin.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "brx_index_escaped.h"
-
-// bit k: byte k of the chunk equals the byte b4 holds four times
-__device__ __forceinline__ uint32_t ie_mask(uint4 v, uint32_t b4) {
-    return ix_nib(ix_eq(v.x, b4)) | (ix_nib(ix_eq(v.y, b4)) << 4) | (ix_nib(ix_eq(v.z, b4)) << 8) | (ix_nib(ix_eq(v.w, b4)) << 12);
-}
-
-// a byte that is none of delimiter, quote and escape, four times: what ix_chunk puts where the stream is not.  In front of a stream
-// it ends any run and toggles nothing, so the stream starts unescaped and outside quotes; behind it it changes no count.
-__device__ __forceinline__ uint32_t ie_filler(uint32_t delim, uint32_t quote, uint32_t escape) {
-    uint32_t f = 0u;
-    while (f == delim || f == quote || f == escape) f++;
-    return f * 0x01010101u;
-}
 
 // One row.  em, qm = the lane's escape and quote bytes; re, rp = the escape bit and the quote parity in front of the row (wave-uniform,
 // moved on to the row's end).  -> bit k: byte k of the lane's chunk is escaped; in: bit k: an odd number of active quotes in front of
@@ -74,34 +62,70 @@ __device__ __forceinline__ uint32_t ie_exit_escape(uint32_t em, uint32_t esc, ui
     return __ballot(lane == (at >> 4) && ((em & ~esc) >> (at & 15u) & 1u)) != 0ull ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_escaped_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
-                                                                               const uint64_t *__restrict__ len, uint32_t n,
-                                                                               uint64_t span, uint32_t delim, uint32_t quote,
-                                                                               uint32_t escape, uint32_t quotes,
-                                                                               const uint64_t *__restrict__ pre, uint64_t max_tiles,
-                                                                               uint64_t *__restrict__ tile_word,
-                                                                               unsigned long long *ticket) {
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles; // (more tiles than `span` allows: a caller's error, nothing is written for them)
-    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
-    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
-    const uint32_t qon = quotes ? 0xFFFFu : 0u, f4 = ie_filler(delim, quotes ? quote : delim, escape);
+// ---- the two dialects of this file ------------------------------------------------------------------------------------------
+// brx_index_set_batch is brx_index_escaped_batch with a set of 1 .. 8 delimiter bytes, and with the escape as optional as the quote.
+// A delimiter never changes the carried state, so "is the delimiter" becomes "is one of the set" in the row body and nothing else
+// moves: ie_row, ie_exit_escape, the tile word, the resolve kernel and ie_select / ie_tile_map are the same.  So there is one count
+// body and one fill body, and a dialect says what a delimiter is and whether an escape byte escapes.
+
+// bit k: byte k of the chunk is one of the nd (1 .. 8) bytes of `set`: the OR of ix_mask over the set, taken before the bits are
+// gathered so that the gathering is done once
+__device__ __forceinline__ uint32_t is_mask(uint4 v, uint64_t set, uint32_t nd) {
+    uint32_t x = 0, y = 0, z = 0, w = 0;
+    for (uint32_t k = 0; k < nd; k++) { // (uniform)
+        const uint32_t d4 = ((uint32_t)set & 0xFFu) * 0x01010101u;
+        set >>= 8;
+        x |= ix_eq(v.x, d4);
+        y |= ix_eq(v.y, d4);
+        z |= ix_eq(v.z, d4);
+        w |= ix_eq(v.w, d4);
+    }
+    return ix_nib(x) | (ix_nib(y) << 4) | (ix_nib(z) << 8) | (ix_nib(w) << 12);
+}
+
+// byte k of the chunk
+__device__ __forceinline__ uint32_t is_byte(uint4 v, uint32_t k) {
+    const uint32_t w = k & 8u ? (k & 4u ? v.w : v.z) : (k & 4u ? v.y : v.x);
+    return w >> (8u * (k & 3u)) & 0xFFu;
+}
+
+// brx_index_escaped_batch: one delimiter byte (d4 = four times), the escape always on -- which the compiler sees
+struct IeByte {
+    uint32_t d4;
+    __device__ __forceinline__ uint32_t delims(uint4 v) const { return ix_mask(v, d4); }
+    __device__ __forceinline__ uint32_t escapes(uint32_t em) const { return em; }
+};
+
+// brx_index_set_batch: the set travels as launch arguments (byte k of `set` for k < nd: SGPRs), the loop over it is wave-uniform;
+// eon = 0 forces the escape mask to 0 as qon = 0 does the quote mask
+struct IeSet {
+    uint64_t set;
+    uint32_t nd, eon;
+    __device__ __forceinline__ uint32_t delims(uint4 v) const { return is_mask(v, set, nd); }
+    __device__ __forceinline__ uint32_t escapes(uint32_t em) const { return em & eon; }
+};
+
+// count: per tile, walked as if it were entered unescaped and outside quotes, the tile word (brx_index_escaped.h)
+template <class D>
+__device__ __forceinline__ void ie_count_tiles(const uint8_t *out, const uint64_t *__restrict__ out_off, const uint64_t *__restrict__ len,
+                                               uint32_t n, uint64_t span, const D d, uint32_t quote, uint32_t escape, uint32_t quotes,
+                                               uint32_t f4, const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                               uint64_t *__restrict__ tile_word, unsigned long long *ticket) {
+    const uint32_t q4 = quote * 0x01010101u, e4 = escape * 0x01010101u, qon = quotes ? 0xFFFFu : 0u;
     const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+    for (TpWalk w = tp_walk(tp_total(pre, n, max_tiles)); w.item < w.total; tp_advance(w, ticket)) {
+        const TpItem it = tp_item(w.item, out, out_off, len, n, pre);
         uint32_t all = 0, odd = 0, rp = 0, re = 0, em = 0, esc = 0;
         uint32_t lead = 4u, rodd = 0; // 4: the leading run of escape bytes has not ended yet
         uint64_t row = it.t0;
         for (uint32_t r = 0; r < it.rows; r++) {
             row = it.t0 + (uint64_t)r * BRX_TP_ROW;
-            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
-            em = ie_mask(v, e4);
-            const uint32_t qm = ie_mask(v, q4) & qon, dm = ie_mask(v, d4);
+            const uint4 v = ix_chunk(out, row, w.lane, it.a, it.e, arena0, arena1, f4);
+            em = d.escapes(ix_mask(v, e4));
+            const uint32_t qm = ix_mask(v, q4) & qon, dm = d.delims(v);
             uint32_t in;
             uint64_t some;
-            esc = ie_row(em, qm, lane, re, rp, in, some);
+            esc = ie_row(em, qm, w.lane, re, rp, in, some);
             if (lead == 4u && some) { // (uniform) once per tile: the first byte that is no escape byte
                 const uint32_t fl = (uint32_t)__ffsll((long long)some) - 1u;
                 const uint32_t k = (uint32_t)__ffs((int)(~em & 0xFFFFu)) - 1u; // (a lane without one: not the lane that is read)
@@ -116,28 +140,70 @@ __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_escaped_count_kernel(c
             odd += __popc(m & in);
         }
         if (lead == 4u) lead = BRX_IE_LEAD_ALL;
-        const uint32_t x = ie_exit_escape(em, esc, lane, row, it.t1);
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) {
-            all += (uint32_t)__shfl_xor((int)all, k);
-            odd += (uint32_t)__shfl_xor((int)odd, k);
-        }
-        if (lane == 0u)
-            tile_word[item] = (uint64_t)(all - odd) | ((uint64_t)odd << BRX_IE_C0_BITS) | ((uint64_t)rp << BRX_IE_PAR_SHIFT) |
-                              ((uint64_t)x << BRX_IE_X_SHIFT) | ((uint64_t)lead << BRX_IE_LEAD_SHIFT) |
-                              ((uint64_t)rodd << BRX_IE_RODD_SHIFT);
-        item = tp_next(ticket, grid_waves, total, lane);
+        const uint32_t x = ie_exit_escape(em, esc, w.lane, row, it.t1);
+        all = tp_wave_sum(all);
+        odd = tp_wave_sum(odd);
+        if (w.lane == 0u)
+            tile_word[w.item] = (uint64_t)(all - odd) | ((uint64_t)odd << BRX_IE_C0_BITS) | ((uint64_t)rp << BRX_IE_PAR_SHIFT) |
+                                ((uint64_t)x << BRX_IE_X_SHIFT) | ((uint64_t)lead << BRX_IE_LEAD_SHIFT) |
+                                ((uint64_t)rodd << BRX_IE_RODD_SHIFT);
     }
 }
 
-// the last i < n with pre[i] <= item (tp_item's search)
-__device__ __forceinline__ uint32_t ie_stream_of(uint64_t item, uint32_t n, const uint64_t *__restrict__ pre) {
-    uint32_t lo_i = 0, hi_i = n;
-    while (hi_i - lo_i > 1u) {
-        const uint32_t mid = lo_i + (hi_i - lo_i) / 2u;
-        if (pre[mid] <= item) lo_i = mid; else hi_i = mid;
+// fill: the count body's row from the tile's real entry state, then tp_emit_row (brx_tiles.h) on the selected mask; next to every
+// position goes the byte that stands there, taken from the chunk in registers, if `what` is given
+template <class D>
+__device__ __forceinline__ void ie_fill_tiles(const uint8_t *out, const uint64_t *__restrict__ out_off, const uint64_t *__restrict__ len,
+                                              uint32_t n, uint64_t span, const D d, uint32_t quote, uint32_t escape, uint32_t quotes,
+                                              uint32_t f4, const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                              const uint64_t *__restrict__ tile_word, const uint64_t *__restrict__ pos_off,
+                                              uint64_t *__restrict__ pos, uint8_t *__restrict__ what, uint64_t pos_total,
+                                              unsigned long long *ticket) {
+    const uint32_t q4 = quote * 0x01010101u, e4 = escape * 0x01010101u, qon = quotes ? 0xFFFFu : 0u;
+    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
+    for (TpWalk w = tp_walk(tp_total(pre, n, max_tiles)); w.item < w.total; tp_advance(w, ticket)) {
+        const TpItem it = tp_item(w.item, out, out_off, len, n, pre);
+        const uint64_t tw = tp_uniform(tile_word[w.item]);
+        // index in pos of the tile's first boundary: the stream's first entry + those of the stream's tiles in front of this one
+        uint64_t base = tp_uniform(pos_off[it.si] + ((tw & BRX_IE_G_MASK) - (tile_word[pre[it.si]] & BRX_IE_G_MASK)));
+        uint32_t rp = (uint32_t)(tw >> BRX_IE_ENTRY_SHIFT) & 1u, re = (uint32_t)(tw >> (BRX_IE_ENTRY_SHIFT + 1u)) & 1u;
+        for (uint32_t r = 0; r < it.rows; r++) {
+            const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
+            const uint4 v = ix_chunk(out, row, w.lane, it.a, it.e, arena0, arena1, f4);
+            uint32_t in;
+            uint64_t some;
+            // (every row: one without a boundary still moves the state on)
+            const uint32_t esc = ie_row(d.escapes(ix_mask(v, e4)), ix_mask(v, q4) & qon, w.lane, re, rp, in, some);
+            const uint32_t m = d.delims(v) & ~esc & ~in; // bit k: byte k of the chunk is a boundary of the stream
+            const uint64_t rel = row + 16u * w.lane - it.a; // offset of the chunk's byte 0 in the stream (m == 0 where that is in front of it)
+            tp_emit_row(m, w.lane, base, pos_total, [&](uint64_t idx, uint32_t k) {
+                pos[idx] = rel + k;
+                if (what) what[idx] = (uint8_t)is_byte(v, k); // (uniform)
+            });
+        }
     }
-    return lo_i;
+}
+
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_escaped_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                                                               const uint64_t *__restrict__ len, uint32_t n,
+                                                                               uint64_t span, uint32_t delim, uint32_t quote,
+                                                                               uint32_t escape, uint32_t quotes,
+                                                                               const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                                                               uint64_t *__restrict__ tile_word,
+                                                                               unsigned long long *ticket) {
+    ie_count_tiles(out, out_off, len, n, span, IeByte{delim * 0x01010101u}, quote, escape, quotes,
+                   ix_filler(delim, 1u, quote, quotes, escape, 1u), pre, max_tiles, tile_word, ticket);
+}
+
+// the tile word is the escaped pass's, BRX_IE_LEAD_DELIM meaning "a byte of the set"
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_set_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                                                           const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
+                                                                           uint64_t set, uint32_t nd, uint32_t quote, uint32_t escape,
+                                                                           uint32_t quotes, uint32_t escapes,
+                                                                           const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                                                           uint64_t *__restrict__ tile_word, unsigned long long *ticket) {
+    ie_count_tiles(out, out_off, len, n, span, IeSet{set, nd, escapes ? 0xFFFFu : 0u}, quote, escape, quotes,
+                   ix_filler(set, nd, quote, quotes, escape, escapes), pre, max_tiles, tile_word, ticket);
 }
 
 // inclusive scan with ie_compose of one map per thread of a 1024-thread workgroup in `part` (1024 words of LDS), the earlier tile being
@@ -154,20 +220,20 @@ __device__ __forceinline__ uint32_t ie_block_scan_1024(uint32_t *part, uint32_t 
     return part[t];
 }
 
-// One workgroup; thread t takes a slice of ceil(total / 1024) tiles, as brx_index_scan_kernel does, and until the last barrier reads
+// One workgroup; thread t takes its slice of the tiles (tp_slice_1024), as brx_index_scan_kernel does, and until the last barrier reads
 // and writes the words of its own slice only: what crosses slices goes through the two scans in LDS.
 __global__ __launch_bounds__(1024) void brx_index_escaped_resolve_kernel(uint32_t n, const uint64_t *__restrict__ pre, uint64_t max_tiles,
                                                                          uint64_t *tile_word, uint64_t *tile_exit,
                                                                          uint64_t *__restrict__ count, uint32_t *__restrict__ open) {
     __shared__ uint64_t part[1024];
     __shared__ uint32_t maps[1024];
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
+    const uint64_t total = tp_total(pre, n, max_tiles);
     const uint32_t t = threadIdx.x;
-    const uint64_t per = (total + 1023u) / 1024u;
-    const uint64_t i0 = per * t < total ? per * t : total, i1 = i0 + per < total ? i0 + per : total; // (thread 1023: i1 == total)
+    const TpSlice sl = tp_slice_1024(total, t);
+    const uint64_t i0 = sl.i0, i1 = sl.i1;
     // 1: the slice's map, tile by tile in order; the scan gives the state in front of the slice (the batch starts in state 0, and its
     // first tile is a stream's first anyway)
-    const uint32_t s0 = i0 < i1 ? ie_stream_of(i0, n, pre) : 0u;
+    const uint32_t s0 = i0 < i1 ? tp_stream_of(i0, n, pre) : 0u;
     uint32_t si = s0;
     uint32_t map = BRX_IE_MAP_IDENTITY;
     for (uint64_t i = i0; i < i1; i++) {
@@ -216,47 +282,22 @@ __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_escaped_fill_kernel(co
                                                                               const uint64_t *__restrict__ pos_off,
                                                                               uint64_t *__restrict__ pos, uint64_t pos_total,
                                                                               unsigned long long *ticket) {
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
-    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
-    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
-    const uint32_t qon = quotes ? 0xFFFFu : 0u, f4 = ie_filler(delim, quotes ? quote : delim, escape);
-    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
-        const uint64_t w = tp_uniform(tile_word[item]);
-        // index in pos of the tile's first record delimiter: the stream's first entry + those of the stream's tiles in front of this one
-        uint64_t base = tp_uniform(pos_off[it.si] + ((w & BRX_IE_G_MASK) - (tile_word[pre[it.si]] & BRX_IE_G_MASK)));
-        uint32_t rp = (uint32_t)(w >> BRX_IE_ENTRY_SHIFT) & 1u, re = (uint32_t)(w >> (BRX_IE_ENTRY_SHIFT + 1u)) & 1u;
-        for (uint32_t r = 0; r < it.rows; r++) {
-            const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
-            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
-            uint32_t in;
-            uint64_t some;
-            const uint32_t esc = ie_row(ie_mask(v, e4), ie_mask(v, q4) & qon, lane, re, rp, in, some); // (every row: it moves the state on)
-            uint32_t m = ie_mask(v, d4) & ~esc & ~in; // bit k: byte k of the chunk is a record delimiter of the stream
-            if (__ballot(m != 0u) == 0ull) continue; // (uniform) a row without one: no position work
-            const uint32_t c = (uint32_t)__popc(m);
-            uint32_t incl = c;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, s);
-                if (lane >= (uint32_t)s) incl += up;
-            }
-            uint64_t idx = base + (incl - c);
-            const uint64_t rel = row + 16u * lane - it.a; // offset of the chunk's byte 0 in the stream (m == 0 where that is in front of it)
-            while (m) {
-                const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
-                m &= m - 1u;
-                if (idx < pos_total) pos[idx] = rel + k;
-                idx++;
-            }
-            base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        item = tp_next(ticket, grid_waves, total, lane);
-    }
+    ie_fill_tiles(out, out_off, len, n, span, IeByte{delim * 0x01010101u}, quote, escape, quotes,
+                  ix_filler(delim, 1u, quote, quotes, escape, 1u), pre, max_tiles, tile_word, pos_off, pos, nullptr, pos_total, ticket);
+}
+
+// `what` may be NULL
+__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_set_fill_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                                                          const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
+                                                                          uint64_t set, uint32_t nd, uint32_t quote, uint32_t escape,
+                                                                          uint32_t quotes, uint32_t escapes,
+                                                                          const uint64_t *__restrict__ pre, uint64_t max_tiles,
+                                                                          const uint64_t *__restrict__ tile_word,
+                                                                          const uint64_t *__restrict__ pos_off, uint64_t *__restrict__ pos,
+                                                                          uint8_t *__restrict__ what, uint64_t pos_total,
+                                                                          unsigned long long *ticket) {
+    ie_fill_tiles(out, out_off, len, n, span, IeSet{set, nd, escapes ? 0xFFFFu : 0u}, quote, escape, quotes,
+                  ix_filler(set, nd, quote, quotes, escape, escapes), pre, max_tiles, tile_word, pos_off, pos, what, pos_total, ticket);
 }
 
 void brx_launch_index_escaped(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint8_t delim,
@@ -277,161 +318,7 @@ void brx_launch_index_escaped(const void *out, const uint64_t *out_off, const ui
                        brx_tp_ticket_b(scratch));
 }
 
-// ---- brx_index_set_batch: the same pass with a set of 1 .. 8 delimiter bytes, and with the escape as optional as the quote --------
-// A delimiter never changes the carried state, so "is the delimiter" becomes "is one of the set" in the row body and nothing else
-// moves: ie_row, ie_exit_escape, the tile word, the resolve kernel above and ie_select / ie_tile_map are the escaped pass's own.  The
-// set travels as launch arguments (byte k of `set` for k < nd: SGPRs), the loop over it is wave-uniform.
-
-// bit k: byte k of the chunk is one of the nd (1 .. 8) bytes of `set`: the OR of ie_mask over the set, taken before the bits are
-// gathered so that the gathering is done once
-__device__ __forceinline__ uint32_t is_mask(uint4 v, uint64_t set, uint32_t nd) {
-    uint32_t x = 0, y = 0, z = 0, w = 0;
-    for (uint32_t k = 0; k < nd; k++) { // (uniform)
-        const uint32_t d4 = ((uint32_t)set & 0xFFu) * 0x01010101u;
-        set >>= 8;
-        x |= ix_eq(v.x, d4);
-        y |= ix_eq(v.y, d4);
-        z |= ix_eq(v.z, d4);
-        w |= ix_eq(v.w, d4);
-    }
-    return ix_nib(x) | (ix_nib(y) << 4) | (ix_nib(z) << 8) | (ix_nib(w) << 12);
-}
-
-// ie_filler for the set: a byte that is no delimiter, not the quote if there is one and not the escape if there is one, four times.
-// At most 10 values are excluded, so the walk ends at 10 or before.
-__device__ __forceinline__ uint32_t is_filler(uint64_t set, uint32_t nd, uint32_t quote, uint32_t quotes, uint32_t escape,
-                                              uint32_t escapes) {
-    uint32_t f = 0u;
-    for (;;) {
-        bool hit = (quotes && f == quote) || (escapes && f == escape);
-        for (uint32_t k = 0; k < nd; k++) hit = hit || f == ((uint32_t)(set >> (8u * k)) & 0xFFu);
-        if (!hit) break;
-        f++;
-    }
-    return f * 0x01010101u;
-}
-
-// byte k of the chunk
-__device__ __forceinline__ uint32_t is_byte(uint4 v, uint32_t k) {
-    const uint32_t w = k & 8u ? (k & 4u ? v.w : v.z) : (k & 4u ? v.y : v.x);
-    return w >> (8u * (k & 3u)) & 0xFFu;
-}
-
-// brx_index_escaped_count_kernel with the union mask; `escapes` = 0 forces the escape mask to 0 as `quotes` = 0 does the quote mask.
-// The tile word is the escaped pass's, BRX_IE_LEAD_DELIM meaning "a byte of the set".
-__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_set_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
-                                                                           const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
-                                                                           uint64_t set, uint32_t nd, uint32_t quote, uint32_t escape,
-                                                                           uint32_t quotes, uint32_t escapes,
-                                                                           const uint64_t *__restrict__ pre, uint64_t max_tiles,
-                                                                           uint64_t *__restrict__ tile_word, unsigned long long *ticket) {
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles; // (more tiles than `span` allows: a caller's error, nothing is written for them)
-    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
-    const uint32_t q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
-    const uint32_t qon = quotes ? 0xFFFFu : 0u, eon = escapes ? 0xFFFFu : 0u;
-    const uint32_t f4 = is_filler(set, nd, quote, quotes, escape, escapes);
-    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
-        uint32_t all = 0, odd = 0, rp = 0, re = 0, em = 0, esc = 0;
-        uint32_t lead = 4u, rodd = 0; // 4: the leading run of escape bytes has not ended yet
-        uint64_t row = it.t0;
-        for (uint32_t r = 0; r < it.rows; r++) {
-            row = it.t0 + (uint64_t)r * BRX_TP_ROW;
-            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
-            em = ie_mask(v, e4) & eon;
-            const uint32_t qm = ie_mask(v, q4) & qon, dm = is_mask(v, set, nd);
-            uint32_t in;
-            uint64_t some;
-            esc = ie_row(em, qm, lane, re, rp, in, some);
-            if (lead == 4u && some) { // (uniform) once per tile: the first byte that is no escape byte
-                const uint32_t fl = (uint32_t)__ffsll((long long)some) - 1u;
-                const uint32_t k = (uint32_t)__ffs((int)(~em & 0xFFFFu)) - 1u; // (a lane without one: not the lane that is read)
-                const uint32_t mine = (k & 15u) | ((dm >> (k & 15u) & 1u) << 4) | ((qm >> (k & 15u) & 1u) << 5);
-                const uint32_t got = (uint32_t)__shfl((int)mine, (int)fl);
-                rodd = got & 1u;
-                lead = row + 16u * fl + (got & 15u) >= it.e ? BRX_IE_LEAD_ALL : got >> 4; // (filler behind the stream's end is no byte of it)
-            }
-            const uint32_t m = dm & ~esc;
-            all += __popc(m);
-            odd += __popc(m & in);
-        }
-        if (lead == 4u) lead = BRX_IE_LEAD_ALL;
-        const uint32_t x = ie_exit_escape(em, esc, lane, row, it.t1);
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) {
-            all += (uint32_t)__shfl_xor((int)all, k);
-            odd += (uint32_t)__shfl_xor((int)odd, k);
-        }
-        if (lane == 0u)
-            tile_word[item] = (uint64_t)(all - odd) | ((uint64_t)odd << BRX_IE_C0_BITS) | ((uint64_t)rp << BRX_IE_PAR_SHIFT) |
-                              ((uint64_t)x << BRX_IE_X_SHIFT) | ((uint64_t)lead << BRX_IE_LEAD_SHIFT) |
-                              ((uint64_t)rodd << BRX_IE_RODD_SHIFT);
-        item = tp_next(ticket, grid_waves, total, lane);
-    }
-}
-
-// brx_index_escaped_fill_kernel with the union mask; next to every position goes the byte that stands there, taken from the chunk in
-// registers (`what` may be NULL)
-__global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_set_fill_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
-                                                                          const uint64_t *__restrict__ len, uint32_t n, uint64_t span,
-                                                                          uint64_t set, uint32_t nd, uint32_t quote, uint32_t escape,
-                                                                          uint32_t quotes, uint32_t escapes,
-                                                                          const uint64_t *__restrict__ pre, uint64_t max_tiles,
-                                                                          const uint64_t *__restrict__ tile_word,
-                                                                          const uint64_t *__restrict__ pos_off, uint64_t *__restrict__ pos,
-                                                                          uint8_t *__restrict__ what, uint64_t pos_total,
-                                                                          unsigned long long *ticket) {
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
-    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
-    const uint32_t q4 = quote * 0x01010101u, e4 = escape * 0x01010101u;
-    const uint32_t qon = quotes ? 0xFFFFu : 0u, eon = escapes ? 0xFFFFu : 0u;
-    const uint32_t f4 = is_filler(set, nd, quote, quotes, escape, escapes);
-    const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
-        const uint64_t w = tp_uniform(tile_word[item]);
-        // index in pos of the tile's first boundary: the stream's first entry + those of the stream's tiles in front of this one
-        uint64_t base = tp_uniform(pos_off[it.si] + ((w & BRX_IE_G_MASK) - (tile_word[pre[it.si]] & BRX_IE_G_MASK)));
-        uint32_t rp = (uint32_t)(w >> BRX_IE_ENTRY_SHIFT) & 1u, re = (uint32_t)(w >> (BRX_IE_ENTRY_SHIFT + 1u)) & 1u;
-        for (uint32_t r = 0; r < it.rows; r++) {
-            const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
-            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
-            uint32_t in;
-            uint64_t some;
-            const uint32_t esc = ie_row(ie_mask(v, e4) & eon, ie_mask(v, q4) & qon, lane, re, rp, in, some); // (every row: it moves the state on)
-            uint32_t m = is_mask(v, set, nd) & ~esc & ~in; // bit k: byte k of the chunk is a boundary of the stream
-            if (__ballot(m != 0u) == 0ull) continue; // (uniform) a row without one: no position work
-            const uint32_t c = (uint32_t)__popc(m);
-            uint32_t incl = c;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, s);
-                if (lane >= (uint32_t)s) incl += up;
-            }
-            uint64_t idx = base + (incl - c);
-            const uint64_t rel = row + 16u * lane - it.a; // offset of the chunk's byte 0 in the stream (m == 0 where that is in front of it)
-            while (m) {
-                const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
-                m &= m - 1u;
-                if (idx < pos_total) {
-                    pos[idx] = rel + k;
-                    if (what) what[idx] = (uint8_t)is_byte(v, k); // (uniform)
-                }
-                idx++;
-            }
-            base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        item = tp_next(ticket, grid_waves, total, lane);
-    }
-}
-
+// ---- brx_index_set_batch: the same launches with the set's two kernels around the one resolve kernel ---------------------------
 void brx_launch_index_set(const void *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span, uint64_t set,
                           uint32_t n_delims, uint8_t quote, uint8_t escape, uint32_t flags, void *scratch, uint64_t max_tiles,
                           uint64_t *count, uint32_t *open, const uint64_t *pos_off, uint64_t *pos, uint8_t *what, uint64_t total,

@@ -2,8 +2,8 @@
 // fields (RFC 4180), on the device (layout: brx_index_quoted.h).
 //
 // A byte of a stream lies inside a quoted field exactly when the number of quote bytes in front of it in the stream is odd (a doubled
-// quote toggles twice), so "inside" is a prefix parity and the pass is the tile pass of brx_index.hip with one more carried bit per
-// lane, row and tile.  Count mode is three launches on the caller's stream, fill mode four:
+// quote toggles twice), so "inside" is a prefix parity and the pass is the tile pass (brx_tiles.h) of brx_index.hip with one more
+// carried bit per lane, row and tile.  Count mode is three launches on the caller's stream, fill mode four:
 //   plan     brx_tiles.hip.
 //   count    a pass over the bytes.  Per tile, taken as if it started outside quotes: c0 = delimiters at even parity, c1 = delimiters
 //            at odd parity, par = parity of its quotes, packed into the tile's scratch word.  If the tile really starts inside a quoted
@@ -11,18 +11,13 @@
 //   resolve  one workgroup, over all tiles of the batch in order: P = exclusive prefix parity of par; tile t of stream i starts with
 //            parity P[t] ^ P[first tile of i]; G = exclusive prefix sum of the counts selected by it.  Then per stream count[i] and
 //            open[i] as differences of G and P between the stream's first tile and its successor's.
-//   fill     the count kernel's row body with the tile's real start parity, then the fill of brx_index.hip on the selected mask.
+//   fill     the count kernel's row body with the tile's real start parity, then tp_emit_row (brx_tiles.h) on the selected mask.
 // Ordering between tiles comes from the kernel boundaries alone: no wave ever waits for a value that another wave of the same launch
 // produces (no chained scan, no look-back), so there is nothing that could spin.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "brx_index_quoted.h"
-
-// bit k: byte k of the chunk equals the byte b4 holds four times
-__device__ __forceinline__ uint32_t iq_mask(uint4 v, uint32_t b4) {
-    return ix_nib(ix_eq(v.x, b4)) | (ix_nib(ix_eq(v.y, b4)) << 4) | (ix_nib(ix_eq(v.z, b4)) << 8) | (ix_nib(ix_eq(v.w, b4)) << 12);
-}
 
 // qm = the lane's quote bytes of a row, rp = the parity in front of the row (wave-uniform, moved on to the row's end).  -> bit k: an
 // odd number of quotes in front of and including byte k of the lane's chunk.  A delimiter is no quote, so for the bytes that are looked
@@ -41,67 +36,41 @@ __device__ __forceinline__ uint32_t iq_inside(uint32_t qm, uint32_t &rp) {
     return (x ^ (0u - carry)) & 0xFFFFu;
 }
 
-// a byte that is neither the delimiter nor the quote, four times: what ix_chunk puts where the stream is not
-__device__ __forceinline__ uint32_t iq_filler(uint32_t delim, uint32_t quote) {
-    uint32_t f = 0u;
-    while (f == delim || f == quote) f++;
-    return f * 0x01010101u;
-}
-
 __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_quoted_count_kernel(const uint8_t *out, const uint64_t *__restrict__ out_off,
                                                                               const uint64_t *__restrict__ len, uint32_t n,
                                                                               uint64_t span, uint32_t delim, uint32_t quote,
                                                                               const uint64_t *__restrict__ pre, uint64_t max_tiles,
                                                                               uint64_t *__restrict__ tile_word,
                                                                               unsigned long long *ticket) {
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles; // (more tiles than `span` allows: a caller's error, nothing is written for them)
-    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
-    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, f4 = iq_filler(delim, quote);
+    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, f4 = ix_filler(delim, 1u, quote, 1u, 0u, 0u);
     const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
+    for (TpWalk w = tp_walk(tp_total(pre, n, max_tiles)); w.item < w.total; tp_advance(w, ticket)) {
+        const TpItem it = tp_item(w.item, out, out_off, len, n, pre);
         uint32_t all = 0, odd = 0, rp = 0;
         for (uint32_t r = 0; r < it.rows; r++) {
-            const uint4 v = ix_chunk(out, it.t0 + (uint64_t)r * BRX_TP_ROW, lane, it.a, it.e, arena0, arena1, f4);
-            const uint32_t dm = iq_mask(v, d4);
-            const uint32_t in = iq_inside(iq_mask(v, q4), rp);
+            const uint4 v = ix_chunk(out, it.t0 + (uint64_t)r * BRX_TP_ROW, w.lane, it.a, it.e, arena0, arena1, f4);
+            const uint32_t dm = ix_mask(v, d4);
+            const uint32_t in = iq_inside(ix_mask(v, q4), rp);
             all += __popc(dm);
             odd += __popc(dm & in);
         }
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) {
-            all += (uint32_t)__shfl_xor((int)all, k);
-            odd += (uint32_t)__shfl_xor((int)odd, k);
-        }
-        if (lane == 0u)
-            tile_word[item] = (uint64_t)(all - odd) | ((uint64_t)odd << BRX_IQ_C0_BITS) | ((uint64_t)rp << BRX_IQ_PAR_SHIFT);
-        item = tp_next(ticket, grid_waves, total, lane);
+        all = tp_wave_sum(all);
+        odd = tp_wave_sum(odd);
+        if (w.lane == 0u)
+            tile_word[w.item] = (uint64_t)(all - odd) | ((uint64_t)odd << BRX_IQ_C0_BITS) | ((uint64_t)rp << BRX_IQ_PAR_SHIFT);
     }
 }
 
-// the last i < n with pre[i] <= item (tp_item's search)
-__device__ __forceinline__ uint32_t iq_stream_of(uint64_t item, uint32_t n, const uint64_t *__restrict__ pre) {
-    uint32_t lo_i = 0, hi_i = n;
-    while (hi_i - lo_i > 1u) {
-        const uint32_t mid = lo_i + (hi_i - lo_i) / 2u;
-        if (pre[mid] <= item) lo_i = mid; else hi_i = mid;
-    }
-    return lo_i;
-}
-
-// One workgroup; thread t takes a slice of ceil(total / 1024) tiles, as brx_index_scan_kernel does.  A word of another thread's slice
+// One workgroup; thread t takes its slice of the tiles (tp_slice_1024), as brx_index_scan_kernel does.  A word of another thread's slice
 // is read only for its bit 63 (P), which step 1 writes and nothing changes behind the barrier that follows it.
 __global__ __launch_bounds__(1024) void brx_index_quoted_resolve_kernel(uint32_t n, const uint64_t *__restrict__ pre, uint64_t max_tiles,
                                                                         uint64_t *tile_word, uint64_t *__restrict__ count,
                                                                         uint32_t *__restrict__ open) {
     __shared__ uint64_t part[1024];
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
+    const uint64_t total = tp_total(pre, n, max_tiles);
     const uint32_t t = threadIdx.x;
-    const uint64_t per = (total + 1023u) / 1024u;
-    const uint64_t i0 = per * t < total ? per * t : total, i1 = i0 + per < total ? i0 + per : total; // (thread 1023: i1 == total)
+    const TpSlice sl = tp_slice_1024(total, t);
+    const uint64_t i0 = sl.i0, i1 = sl.i1;
     // 1: P[t], the parity of the quotes of all tiles in front of tile t, into bit 63 of the tile's word
     uint64_t par = 0;
     for (uint64_t i = i0; i < i1; i++) par ^= tile_word[i] >> BRX_IQ_PAR_SHIFT & 1u;
@@ -114,7 +83,7 @@ __global__ __launch_bounds__(1024) void brx_index_quoted_resolve_kernel(uint32_t
     if (t == 1023u) tile_word[total] = p << BRX_IQ_P_SHIFT;
     __syncthreads();
     // 2: the parity a tile of stream i starts with is P[t] ^ P[first tile of i] (every stream starts outside quotes); it selects c1 or c0
-    const uint32_t s0 = i0 < i1 ? iq_stream_of(i0, n, pre) : 0u;
+    const uint32_t s0 = i0 < i1 ? tp_stream_of(i0, n, pre) : 0u;
     uint32_t si = s0;
     uint64_t sum = 0;
     for (uint64_t i = i0; i < i1; i++) {
@@ -155,43 +124,22 @@ __global__ __launch_bounds__(BRX_TP_WG, 8) void brx_index_quoted_fill_kernel(con
                                                                              const uint64_t *__restrict__ pos_off,
                                                                              uint64_t *__restrict__ pos, uint64_t pos_total,
                                                                              unsigned long long *ticket) {
-    const uint64_t total = pre[n] < max_tiles ? pre[n] : max_tiles;
-    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t grid_waves = (uint64_t)gridDim.x * waves_per_wg;
-    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, f4 = iq_filler(delim, quote);
+    const uint32_t d4 = delim * 0x01010101u, q4 = quote * 0x01010101u, f4 = ix_filler(delim, 1u, quote, 1u, 0u, 0u);
     const uint64_t arena0 = (uint64_t)(uintptr_t)out, arena1 = arena0 + span;
-    uint64_t item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
-    while (item < total) {
-        const TpItem it = tp_item(item, out, out_off, len, n, pre);
-        const uint64_t w = tp_uniform(tile_word[item]);
+    for (TpWalk w = tp_walk(tp_total(pre, n, max_tiles)); w.item < w.total; tp_advance(w, ticket)) {
+        const TpItem it = tp_item(w.item, out, out_off, len, n, pre);
+        const uint64_t tw = tp_uniform(tile_word[w.item]);
         // index in pos of the tile's first record delimiter: the stream's first entry + those of the stream's tiles in front of this one
-        uint64_t base = tp_uniform(pos_off[it.si] + ((w & BRX_IQ_G_MASK) - (tile_word[pre[it.si]] & BRX_IQ_G_MASK)));
-        uint32_t rp = (uint32_t)(w >> BRX_IQ_START_SHIFT) & 1u;
+        uint64_t base = tp_uniform(pos_off[it.si] + ((tw & BRX_IQ_G_MASK) - (tile_word[pre[it.si]] & BRX_IQ_G_MASK)));
+        uint32_t rp = (uint32_t)(tw >> BRX_IQ_START_SHIFT) & 1u;
         for (uint32_t r = 0; r < it.rows; r++) {
             const uint64_t row = it.t0 + (uint64_t)r * BRX_TP_ROW;
-            const uint4 v = ix_chunk(out, row, lane, it.a, it.e, arena0, arena1, f4);
-            const uint32_t in = iq_inside(iq_mask(v, q4), rp); // (every row: one without a delimiter still moves the parity on)
-            uint32_t m = iq_mask(v, d4) & ~in; // bit k: byte k of the chunk is a record delimiter of the stream
-            if (__ballot(m != 0u) == 0ull) continue; // (uniform) a row without one: no position work
-            const uint32_t c = (uint32_t)__popc(m);
-            uint32_t incl = c;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, s);
-                if (lane >= (uint32_t)s) incl += up;
-            }
-            uint64_t idx = base + (incl - c);
-            const uint64_t rel = row + 16u * lane - it.a; // offset of the chunk's byte 0 in the stream (m == 0 where that is in front of it)
-            while (m) {
-                const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
-                m &= m - 1u;
-                if (idx < pos_total) pos[idx] = rel + k;
-                idx++;
-            }
-            base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            const uint4 v = ix_chunk(out, row, w.lane, it.a, it.e, arena0, arena1, f4);
+            const uint32_t in = iq_inside(ix_mask(v, q4), rp); // (every row: one without a delimiter still moves the parity on)
+            const uint32_t m = ix_mask(v, d4) & ~in; // bit k: byte k of the chunk is a record delimiter of the stream
+            const uint64_t rel = row + 16u * w.lane - it.a; // offset of the chunk's byte 0 in the stream (m == 0 where that is in front of it)
+            tp_emit_row(m, w.lane, base, pos_total, [&](uint64_t idx, uint32_t k) { pos[idx] = rel + k; });
         }
-        item = tp_next(ticket, grid_waves, total, lane);
     }
 }
 

@@ -1,11 +1,14 @@
 // brx_tiles.h -- the tile pass: the one shape of every pass that walks the decoded streams of a device-resident batch (brx_digest.hip,
-// brx_index.hip, brx_index_quoted.hip, brx_find.hip; the host side of its scratch in brx_api.cpp).
+// brx_index.hip, brx_index_quoted.hip, brx_index_escaped.hip, brx_find.hip; the host side of its scratch in brx_api.cpp).
 //
 // A work item is one (stream, tile) pair, a tile = 64 KiB of the stream's 1 KiB aligned address range.  The host never learns a length,
 // so a one-workgroup plan kernel (brx_tiles.hip) computes tiles per stream and their exclusive prefix sum pre[0 .. n] on the device.
 // A pass over the bytes is a persistent grid of 4 workgroups of 8 waves per CU: a wave's first item is its index in the grid, the
-// following ones come from a ticket counter; the stream of an item is found by binary search in pre[].  The wave walks its tile in
-// aligned 1 KiB rows, 16 B per lane.  What a pass does with a row, and what it loads at a stream's edges, is its own.
+// following ones come from a ticket counter (TpWalk); the stream of an item is found by binary search in pre[] (tp_stream_of).  The
+// wave walks its tile in aligned 1 KiB rows, 16 B per lane.  What a pass does with a row, and what it loads at a stream's edges, is
+// its own: a kernel states its per-tile body.  What several bodies do the same way stands here too: the sum over a wave's lanes
+// (tp_wave_sum), the positions of a row's set bits in stream order (tp_emit_row), and for the one-workgroup kernels between two
+// passes the slice of a thread (tp_slice_1024) and the scan over the slices (tp_block_scan_1024).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -67,18 +70,23 @@ struct TpItem {
 };
 
 // the stream of an item: the last i < n with pre[i] <= item (streams without tiles share their successor's value and lose)
-__device__ __forceinline__ TpItem tp_item(uint64_t item, const uint8_t *out, const uint64_t *__restrict__ out_off,
-                                          const uint64_t *__restrict__ len, uint32_t n, const uint64_t *__restrict__ pre) {
+__device__ __forceinline__ uint32_t tp_stream_of(uint64_t item, uint32_t n, const uint64_t *__restrict__ pre) {
     uint32_t lo_i = 0, hi_i = n;
     while (hi_i - lo_i > 1u) {
         const uint32_t mid = lo_i + (hi_i - lo_i) / 2u;
         if (pre[mid] <= item) lo_i = mid; else hi_i = mid;
     }
+    return lo_i;
+}
+
+// an item's stream and tile (all of it wave-uniform)
+__device__ __forceinline__ TpItem tp_item(uint64_t item, const uint8_t *out, const uint64_t *__restrict__ out_off,
+                                          const uint64_t *__restrict__ len, uint32_t n, const uint64_t *__restrict__ pre) {
     TpItem it;
-    it.si = lo_i;
-    it.a = (uint64_t)(uintptr_t)out + out_off[lo_i];
-    it.e = it.a + len[lo_i];
-    it.t0 = (it.a & ~(uint64_t)(BRX_TP_ROW - 1u)) + (item - pre[lo_i]) * BRX_TP_TILE;
+    it.si = tp_stream_of(item, n, pre);
+    it.a = (uint64_t)(uintptr_t)out + out_off[it.si];
+    it.e = it.a + len[it.si];
+    it.t0 = (it.a & ~(uint64_t)(BRX_TP_ROW - 1u)) + (item - pre[it.si]) * BRX_TP_TILE;
     it.t1 = it.t0 + BRX_TP_TILE < it.e ? it.t0 + BRX_TP_TILE : it.e;
     it.rows = (uint32_t)((it.t1 - it.t0 + BRX_TP_ROW - 1u) / BRX_TP_ROW);
     return it;
@@ -93,5 +101,77 @@ __device__ __forceinline__ uint64_t tp_next(unsigned long long *ticket, uint64_t
     }
     next = (unsigned long long)__shfl((long long)next, 0);
     return tp_uniform(grid_waves + next);
+}
+
+// the tiles a pass walks: those of the batch, but no more than its scratch has words for (more tiles than `span` allows: a caller's
+// error, nothing is written for them)
+__device__ __forceinline__ uint64_t tp_total(const uint64_t *__restrict__ pre, uint32_t n, uint64_t max_tiles) {
+    return pre[n] < max_tiles ? pre[n] : max_tiles;
+}
+
+// A wave's walk over the items of a pass of BRX_TP_WG threads per workgroup:
+//     for (TpWalk w = tp_walk(total); w.item < w.total; tp_advance(w, ticket)) { const TpItem it = tp_item(w.item, ...); ... }
+struct TpWalk {
+    uint32_t lane;
+    uint64_t grid_waves;
+    uint64_t total;
+    uint64_t item; // (wave-uniform)
+};
+
+__device__ __forceinline__ TpWalk tp_walk(uint64_t total) {
+    const uint32_t waves_per_wg = BRX_TP_WG / 64u;
+    TpWalk w;
+    w.lane = threadIdx.x & 63u;
+    w.grid_waves = (uint64_t)gridDim.x * waves_per_wg;
+    w.total = total;
+    w.item = tp_uniform((uint64_t)blockIdx.x * waves_per_wg + (threadIdx.x >> 6));
+    return w;
+}
+
+__device__ __forceinline__ void tp_advance(TpWalk &w, unsigned long long *ticket) {
+    w.item = tp_next(ticket, w.grid_waves, w.total, w.lane);
+}
+
+// the sum of v over the wave's 64 lanes, in every lane
+__device__ __forceinline__ uint32_t tp_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) v += (uint32_t)__shfl_xor((int)v, k);
+    return v;
+}
+
+// thread t of a 1024-thread workgroup takes the tiles [i0, i1) of `total`: ceil(total / 1024) each, in order (thread 1023: i1 == total)
+struct TpSlice {
+    uint64_t i0, i1;
+};
+
+__device__ __forceinline__ TpSlice tp_slice_1024(uint64_t total, uint32_t t) {
+    const uint64_t per = (total + 1023u) / 1024u;
+    TpSlice s;
+    s.i0 = per * t < total ? per * t : total;
+    s.i1 = s.i0 + per < total ? s.i0 + per : total;
+    return s;
+}
+
+// One row's entries.  m = the lane's 16-bit mask (bit k: byte k of its chunk is reported), base = the index of the row's first entry
+// (wave-uniform, moved on to the next row's).  The entries are numbered in stream order by a wave prefix sum of the lanes' population
+// counts (__shfl_up, no LDS memory); store(idx, k) is called for every set bit k whose index idx lies below pos_total.
+template <class Store>
+__device__ __forceinline__ void tp_emit_row(uint32_t m, uint32_t lane, uint64_t &base, uint64_t pos_total, Store store) {
+    if (__ballot(m != 0u) == 0ull) return; // (uniform) a row without one: no position work
+    const uint32_t c = (uint32_t)__popc(m);
+    uint32_t incl = c;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, s);
+        if (lane >= (uint32_t)s) incl += up;
+    }
+    uint64_t idx = base + (incl - c);
+    while (m) {
+        const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
+        m &= m - 1u;
+        if (idx < pos_total) store(idx, k);
+        idx++;
+    }
+    base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 }
 #endif

@@ -22,7 +22,7 @@ static bool in_set(uint8_t b) {
     for (uint32_t k = 0; k < ND; k++) if (b == (uint8_t)(SET >> (8 * k))) return true;
     return false;
 }
-// is_filler of the kernels
+// ix_filler of the kernels (brx_index.h)
 static uint8_t filler() {
     uint32_t f = 0;
     for (;;) {

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Write profiles/INDEX.md: the hand-kept table "which file backs which number of DESIGN.md" (tools/profiles_index_head.md) followed by
-a generated listing of every file under profiles/ with what kind of evidence it is (by name pattern)."""
+a generated listing of every file under profiles/ with what kind of evidence it is (a file keeps the description that the listing
+already has for it; a new one gets one by name pattern, else its own first line)."""
 import os
 import re
 
@@ -36,14 +37,19 @@ def main():
     names = sorted(os.listdir(P))
     rounds = {}
     for n in names:
-        m = re.search(r"(?:^|_)(r0\d)", n)
+        m = re.search(r"(?:^|_)(r\d\d)", n)
         rounds.setdefault(m.group(1) if m else "other", []).append(n)
+    kept = {}  # a description written by hand into the listing stays
+    for line in open(os.path.join(P, "INDEX.md"), errors="replace") if os.path.exists(os.path.join(P, "INDEX.md")) else ():
+        m = re.fullmatch(r"\* `([^`]+)` — (.+)\n?", line)
+        if m:
+            kept[m.group(1)] = m.group(2)
     out = [head.rstrip(), "", "## Every file", ""]
     for r in sorted(rounds, reverse=True):
         out.append("### %s" % r)
         out.append("")
         for n in rounds[r]:
-            d = describe(n)
+            d = kept.get(n) or describe(n)
             if d is None:
                 first = ""
                 try:
