@@ -52,6 +52,7 @@ MEMBER_MISSING, MEMBER_SCALAR, MEMBER_OBJECT, MEMBER_ARRAY, MEMBER_BAD = 0, 1, 2
 MEMBER_LONG_KEY, MEMBER_ESCAPED_KEY, MEMBER_UNBALANCED = 1, 2, 4  # BRX_MEMBER_LONG_KEY ... (the bits of line_flags)
 ELEMENTS_OK, ELEMENTS_NONE, ELEMENTS_NOT_ARRAY, ELEMENTS_UNCLOSED, ELEMENTS_MISMATCH = 0, 1, 2, 3, 4  # BRX_ELEMENTS_OK ... (brx_elements_batch)
 ELEMENTS_MAX_BLANK = 64  # BRX_ELEMENTS_MAX_BLANK
+OBJECT_OK, OBJECT_NONE, OBJECT_NOT_OBJECT, OBJECT_UNCLOSED, OBJECT_MISMATCH = 0, 1, 2, 3, 4  # BRX_OBJECT_OK ... (brx_object_batch)
 
 
 class BrxError(RuntimeError):
@@ -137,6 +138,9 @@ def load_library():
                                    P, P, P, P, P]
     L.brx_elements_batch.restype = ctypes.c_int
     L.brx_elements_batch.argtypes = [P, P, P, P, U32, U64, P, P, P, P, U64, P, P, U64, P, P, P, P, U64, P, P, P, P]
+    L.brx_object_batch.restype = ctypes.c_int
+    L.brx_object_batch.argtypes = [P, P, P, P, U32, U64, P, P, P, P, U64, P, P, U64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), U32,
+                                   P, P, P, P, P, P, P, P]
     L.brx_status_str.restype = ctypes.c_char_p
     L.brx_status_str.argtypes = [ctypes.c_int32]
     L.brx_last_error.restype = ctypes.c_char_p
@@ -194,7 +198,8 @@ EXPORTED_SYMBOLS = ["brx_ctx_create", "brx_ctx_destroy", "brx_decode_batch", "br
                     "brx_node_size", "brx_node_ctx", "brx_node_set_option", "brx_node_decode_batch", "brx_node_last_timing", "brx_node_deal",
                     "brx_stream_advance", "brx_stream_ready", "brx_digest_batch", "brx_index_batch", "brx_index_quoted_batch",
                     "brx_find_batch", "brx_index_escaped_batch", "brx_index_set_batch", "brx_take_batch", "brx_hash_batch",
-                    "brx_parse_batch", "brx_parse_time_batch", "brx_unescape_batch", "brx_member_batch", "brx_elements_batch"]
+                    "brx_parse_batch", "brx_parse_time_batch", "brx_unescape_batch", "brx_member_batch", "brx_elements_batch",
+                    "brx_object_batch"]
 # Exported names with a digit in them.  They are kept apart because tests/test_abi.py compares EXPORTED_SYMBOLS with the names it reads
 # from include/brx.h by the pattern brx_[a-z_]+, which such a name does not match; tests/test_parse_f64_abi.py holds this list to the
 # header and to the library.
@@ -886,6 +891,76 @@ class Context:
             self.elements_batch_device(*head, None, None, None, el_off.data_ptr(), E, el_stream.data_ptr(), el_rec.data_ptr(),
                                        el_kind.data_ptr(), hip_stream=hs)
         return n_elem, el_off, status[:m], end[:m], el_stream[:E], el_rec[:E], el_kind[:E]
+
+    def object_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, what_ptr, n_pos, sel_stream_ptr,
+                            sel_rec_ptr, m, names, n_members_ptr, status_ptr=None, end_ptr=None, mem_stream_ptr=None, mem_rec_ptr=None,
+                            mem_kind_ptr=None, obj_flags_ptr=None, hip_stream=None):
+        """brx_object_batch on raw device pointers: the named members of the nested JSON objects whose openers the pairs (sel_stream,
+        sel_rec) name (sel_rec = the boundary index of a '{', as member_batch_device gives it for MEMBER_OBJECT and
+        elements_batch_device for an object element), under the positions count / pos_off / pos / what of a fill-mode index_set_batch
+        call with delims b'{}[]:,\\n'.  `names`: a sequence of 0 .. 8 distinct bytes objects of 1 .. 32 bytes, host memory, taken
+        during the call.  Entry (q, j) at q * m + j: mem_stream (uint32), mem_rec (uint64) and mem_kind (uint8, MEMBER_MISSING ...
+        MEMBER_BAD) of the last member of object j whose key is names[q]; n_members[j] (uint64), status[j] (uint8, OBJECT_OK ...
+        OBJECT_MISMATCH), end[j] (uint64, the closer's boundary index) and obj_flags[j] (uint8, MEMBER_LONG_KEY | MEMBER_ESCAPED_KEY)
+        may each be None.  No names: the extent mode, n_members (required), status and end alone.  Nothing at or beyond
+        len(names) * m is written."""
+        names = [bytes(x) for x in names]
+        packed = b"".join(x[:MEMBER_MAX_NAME].ljust(MEMBER_MAX_NAME, b"\0") for x in names)
+        lens = (ctypes.c_uint32 * max(len(names), 1))(*[len(x) for x in names])
+        rc = self._lib.brx_object_batch(self._h, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, what_ptr, n_pos,
+                                        sel_stream_ptr, sel_rec_ptr, m, packed if names else None, lens if names else None, len(names),
+                                        n_members_ptr, status_ptr, end_ptr, mem_stream_ptr, mem_rec_ptr, mem_kind_ptr, obj_flags_ptr,
+                                        hip_stream)
+        if rc != 0:
+            raise BrxError("brx_object_batch failed (%d): %s" % (rc, self._lib.brx_last_error().decode()))
+
+    def object_batch(self, out, out_off, out_len, count, pos_off, pos, what, sel_stream, sel_rec, names=(), stream=None):
+        """The named members of nested JSON objects as selections for the record calls, found on the device.  out, out_off, out_len and
+        stream as for index_batch; count, pos_off, pos, what as index_set_batch(delims=b'{}[]:,\\n') returned them; (sel_stream,
+        sel_rec): the openers, as one row of member_batch's sel_stream / sel_rec or elements_batch's el_stream / el_rec -- entries
+        that are not MEMBER_OBJECT may stay in it; names: 0 .. 8 distinct keys (bytes, 1 .. 32 of them each).
+        Returns (n_members, status, end, mem_stream, mem_rec, mem_kind, obj_flags): per entry the number of members (int64), the status
+        (uint8: OBJECT_OK, OBJECT_NONE for MISSING, OBJECT_NOT_OBJECT, OBJECT_UNCLOSED, OBJECT_MISMATCH for an object closed by ']')
+        and the boundary index of the closer (int64, -1 for NONE and NOT_OBJECT); mem_stream (int32), mem_rec (int64) and mem_kind
+        (uint8) of shape [len(names), m]: row q is the selection of names[q] for a record call, entry j its value in object j -- the
+        LAST member with that key, as json.loads has it; MEMBER_SCALAR (the record is the value), MEMBER_OBJECT (mem_rec is again an
+        opener: a second object_batch call goes one level down), MEMBER_ARRAY (an opener for elements_batch), MEMBER_BAD or
+        MEMBER_MISSING (mem_rec -1: selects nothing); obj_flags[j] (uint8): MEMBER_LONG_KEY, MEMBER_ESCAPED_KEY.  Without names the
+        last four are None: the extent of every object alone.  One call, nothing read back.  The scores under "meta" and the prices
+        of the objects in "items", rows {"meta":{"lang":"en","score":0.93},"items":[{"id":1,"price":2.5}]}:
+            count, _, pos_off, pos, what = ctx.index_set_batch(out, out_off, out_len, delims=b'{}[]:,\\n')
+            lines, line_off, ss, sr, kind, flags = ctx.member_batch(out, out_off, out_len, count, pos_off, pos, what, [b"meta", b"items"])
+            _, st, end, ms, mr, mk, _ = ctx.object_batch(out, out_off, out_len, count, pos_off, pos, what, ss[0], sr[0], [b"score"])
+            score, vst = ctx.parse_f64_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=ms[0], sel_rec=mr[0], spaces=True)
+            n_elem, el_off, est, eend, es, er, ek = ctx.elements_batch(out, out_off, out_len, count, pos_off, pos, what, ss[1], sr[1])
+            _, st, end, ms, mr, mk, _ = ctx.object_batch(out, out_off, out_len, count, pos_off, pos, what, es, er, [b"price"])
+            price, vst = ctx.parse_f64_batch(out, out_off, out_len, count, pos_off, pos, sel_stream=ms[0], sel_rec=mr[0], spaces=True)"""
+        import torch
+        n, dev, Q = int(out_len.numel()), out.device, len(names)
+        hs = stream.cuda_stream if stream is not None else None
+        with _on(stream):
+            sel_stream = sel_stream.to(torch.int32).contiguous()
+            sel_rec = sel_rec.to(torch.int64).contiguous()
+            m = int(sel_stream.numel())
+            n_members = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+            status = torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+            end = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+            mem_stream = mem_rec = mem_kind = obj_flags = None
+            if Q:  # (the buffers are exactly [Q, m]: entry (q, j) is at q * m + j)
+                mem_stream = torch.empty((Q, max(m, 1)), dtype=torch.int32, device=dev)
+                mem_rec = torch.empty((Q, max(m, 1)), dtype=torch.int64, device=dev)
+                mem_kind = torch.empty((Q, max(m, 1)), dtype=torch.uint8, device=dev)
+                obj_flags = torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+        _rec_sync(out, stream)
+        self.object_batch_device(out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), n, int(out.numel()), count.data_ptr(),
+                                 pos_off.data_ptr(), pos.data_ptr() if pos.numel() else None, what.data_ptr() if what.numel() else None,
+                                 int(pos.numel()), sel_stream.data_ptr() if m else None, sel_rec.data_ptr() if m else None, m, names,
+                                 n_members.data_ptr(), status.data_ptr(), end.data_ptr(), mem_stream.data_ptr() if Q else None,
+                                 mem_rec.data_ptr() if Q else None, mem_kind.data_ptr() if Q else None,
+                                 obj_flags.data_ptr() if Q else None, hip_stream=hs)
+        if not Q:
+            return n_members[:m], status[:m], end[:m], None, None, None, None
+        return n_members[:m], status[:m], end[:m], mem_stream[:, :m], mem_rec[:, :m], mem_kind[:, :m], obj_flags[:m]
 
     def parse_f64_batch_device(self, out_ptr, out_off_ptr, len_ptr, n, span, count_ptr, pos_off_ptr, pos_ptr, n_pos, delim_len, flags,
                                sel_stream_ptr, sel_rec_ptr, m, quote, val_ptr, status_ptr, hip_stream=None):

@@ -9,8 +9,8 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB_PATH = os.path.join(PKG, "libbrx.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["brx_kernels.hip", "brx_kernels_l1.hip", "brx_kernels_l2.hip", "brx_kernels_l3.hip", "brx_kernels_l4.hip", "brx_kernels_s.hip", "brx_gen.hip", "brx_util.hip", "brx_tiles.hip", "brx_digest.hip", "brx_index.hip", "brx_index_quoted.hip", "brx_index_escaped.hip", "brx_find.hip", "brx_take.hip", "brx_hash.hip", "brx_parse.hip", "brx_parse_f64.hip", "brx_parse_time.hip", "brx_unescape.hip", "brx_member.hip", "brx_elements.hip", "brx_api.cpp", "brx_node.cpp"]
-DEPS = SOURCES + ["brx_device.h", "brx_layout.h", "brx_tiles.h", "brx_digest.h", "brx_index.h", "brx_index_quoted.h", "brx_index_escaped.h", "brx_find.h", "brx_take.h", "brx_record_dev.h", "brx_hash.h", "brx_parse.h", "brx_parse_f64.h", "brx_parse_time.h", "brx_unescape.h", "brx_member.h", "brx_elements.h", "brx_pow5.h", "brx_internal.h", "brx_plan.h", "brx_small.h", "brx_hot.S", "brx_lens.S", os.path.join("..", "host", "brx_walk.cpp"), os.path.join("..", "..", "include", "brx.h"),
+SOURCES = ["brx_kernels.hip", "brx_kernels_l1.hip", "brx_kernels_l2.hip", "brx_kernels_l3.hip", "brx_kernels_l4.hip", "brx_kernels_s.hip", "brx_gen.hip", "brx_util.hip", "brx_tiles.hip", "brx_digest.hip", "brx_index.hip", "brx_index_quoted.hip", "brx_index_escaped.hip", "brx_find.hip", "brx_take.hip", "brx_hash.hip", "brx_parse.hip", "brx_parse_f64.hip", "brx_parse_time.hip", "brx_unescape.hip", "brx_member.hip", "brx_elements.hip", "brx_object.hip", "brx_api.cpp", "brx_node.cpp"]
+DEPS = SOURCES + ["brx_device.h", "brx_layout.h", "brx_tiles.h", "brx_digest.h", "brx_index.h", "brx_index_quoted.h", "brx_index_escaped.h", "brx_find.h", "brx_take.h", "brx_record_dev.h", "brx_hash.h", "brx_parse.h", "brx_parse_f64.h", "brx_parse_time.h", "brx_unescape.h", "brx_member.h", "brx_elements.h", "brx_object.h", "brx_pow5.h", "brx_internal.h", "brx_plan.h", "brx_small.h", "brx_hot.S", "brx_lens.S", os.path.join("..", "host", "brx_walk.cpp"), os.path.join("..", "..", "include", "brx.h"),
                   os.path.join("..", "tables", "dictionary.bin"), os.path.join("..", "tables", "context_lut.bin"),
                   os.path.join("..", "tables", "transforms.bin"), os.path.join("..", "tables", "gen_header.bin"), os.path.join("..", "build.py")]
 

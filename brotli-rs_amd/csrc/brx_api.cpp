@@ -41,6 +41,7 @@
 #include "brx_unescape.h"
 #include "brx_member.h"
 #include "brx_elements.h"
+#include "brx_object.h"
 #include "brx_internal.h"
 #include "brx_plan.h"
 
@@ -1747,6 +1748,53 @@ extern "C" int brx_elements_batch(brx_ctx *c, const uint8_t *out, const uint64_t
     x.what = what; x.n_elem = n_elem; x.status = status; x.end = end;
     x.el_off = el_off; x.total = total; x.el_stream = el_stream; x.el_rec = el_rec; x.el_kind = el_kind;
     return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_elements(x, st); return launched(); });
+    BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
+}
+
+// ---- the named members of the nested JSON objects behind a selection of openers, and their extent (brx_object.hip) ------------
+extern "C" int brx_object_batch(brx_ctx *c, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                                const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                                const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, const uint8_t *names, const uint32_t *name_len,
+                                uint32_t n_names, uint64_t *n_members, uint8_t *status, uint64_t *end, uint32_t *mem_stream, uint64_t *mem_rec,
+                                uint8_t *mem_kind, uint8_t *obj_flags, void *hip_stream) {
+    BRX_GUARD_BEGIN
+    const char *call = "brx_object_batch";
+    static_assert(BRX_OB_OK == BRX_OBJECT_OK && BRX_OB_NONE == BRX_OBJECT_NONE && BRX_OB_NOT_OBJECT == BRX_OBJECT_NOT_OBJECT &&
+                  BRX_OB_UNCLOSED == BRX_OBJECT_UNCLOSED && BRX_OB_MISMATCH == BRX_OBJECT_MISMATCH, "the kernel's values are brx.h's");
+    static_assert(BRX_OB_LONG <= 254u, "a member's tag in the lane path is one byte");
+    if (!c) return refuse(call, "ctx is NULL");
+    if (n_names > BRX_MEMBER_MAX_NAMES) return refuse(call, "n_names is not 0 .. 8");
+    if (n_names > 0 && (!names || !name_len)) return refuse(call, "names or name_len is NULL with n_names > 0");
+    for (uint32_t q = 0; q < n_names; q++)
+        if (name_len[q] == 0 || name_len[q] > BRX_MEMBER_MAX_NAME) return refuse(call, "a name_len is not 1 .. 32");
+    // the names as the kernel takes them: launch arguments (read here: the caller may reuse `names` at once)
+    BrxMbNames nm;
+    memset(&nm, 0, sizeof nm);
+    nm.n = n_names;
+    for (uint32_t q = 0; q < n_names; q++) {
+        nm.len[q] = name_len[q];
+        memcpy(nm.w[q], names + (size_t)BRX_MEMBER_MAX_NAME * q, name_len[q]);
+        for (uint32_t p = 0; p < q; p++)
+            if (nm.len[p] == nm.len[q] && !memcmp(nm.w[p], nm.w[q], sizeof nm.w[q])) return refuse(call, "a name stands twice in names");
+    }
+    if ((sel_stream == nullptr) != (sel_rec == nullptr)) return refuse(call, "sel_stream and sel_rec go together");
+    const int given = (mem_stream != nullptr) + (mem_rec != nullptr) + (mem_kind != nullptr);
+    if (n_names > 0 && given != 3) return refuse(call, "mem_stream, mem_rec or mem_kind is NULL with n_names > 0");
+    if (n_names == 0 && (given != 0 || obj_flags)) return refuse(call, "mem_stream, mem_rec, mem_kind or obj_flags is given in extent mode");
+    if (n_names == 0 && !n_members) return refuse(call, "n_members is NULL in extent mode");
+    if (m == 0) return BRX_SUCCESS;
+    if (!sel_stream) return refuse(call, "sel_stream and sel_rec are NULL");
+    if (n > 0 && (!out_off || !len || !count || !pos_off)) return refuse(call, "NULL table");
+    if ((!pos || !what) && n_pos > 0) return refuse(call, "pos or what is NULL with n_pos > 0");
+    if (brx_ix_max_tiles(n, span) > (uint64_t)1 << 40) return refuse(call, "span out of range");
+    // the grid follows from m alone; n_pos bounds every index into the tables, and m < 2^39 with n_names <= 8 keeps every q * m + j in range
+    if ((m + 255u) / 256u > 0x7fffffffull) return refuse(call, "m out of range");
+    if (n_pos > (uint64_t)1 << 40) return refuse(call, "n_pos out of range");
+    BrxObArgs x;
+    x.a = rec_args(out, out_off, len, n, span, count, pos_off, pos, n_pos, 1u, BRX_TAKE_NO_DELIM, sel_stream, sel_rec, m);
+    x.what = what; x.n_members = n_members; x.status = status; x.end = end;
+    x.mem_stream = mem_stream; x.mem_rec = mem_rec; x.mem_kind = mem_kind; x.obj_flags = obj_flags;
+    return run_locked(c, hip_stream, [&](hipStream_t st) { brx_launch_object(x, nm, st); return launched(); });
     BRX_GUARD_END(BRX_ERR_OUT_OF_MEMORY, BRX_ERR_HIP)
 }
 

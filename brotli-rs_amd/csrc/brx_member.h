@@ -157,15 +157,18 @@ BRX_TAKE_HD void brx_mb_flag(M &mem, const BrxMbArgs &x, uint64_t i, uint64_t li
 
 BRX_TAKE_HD uint64_t brx_mb_below(uint32_t n) { return n >= 64u ? ~(uint64_t)0 : ((uint64_t)1 << n) - 1u; }
 
-// The member whose ':' is boundary k of stream i, in line `line`: its key record against the names.  Returns the flag bits it adds
-// to its line.  Loads the record's bytes (at most 64) once for the masks and the key's body (at most 32) once more where it is placed.
-template <class M>
-BRX_TAKE_HD uint32_t brx_mb_member(M &mem, const BrxMbArgs &x, const BrxMbNames &nm, uint64_t i, uint64_t k, uint64_t line) {
-    const BrxTakeRec r = brx_take_record(mem, x.a, i, k);
+// The key record of the member whose ':' is boundary k of stream i (a: flags = BRX_TAKE_F_NO_DELIM, delim_len = 1), trimmed.  Returns
+// the flag bits it adds.  Where '"', bn = 1 .. 32 bytes and '"' are left, `carries(key)` is called with those bytes as a name is kept;
+// the caller says there which names they are (brx_mb_key_is) and what follows.  Shared with brx_object.h.  Loads the record's bytes (at
+// most 64) once for the masks and the key's body (at most 32) once more where it is placed.
+struct BrxMbKey { uint32_t bn; BrxTake128 b0, b1; };
+template <class M, class F>
+BRX_TAKE_HD uint32_t brx_mb_key(M &mem, const BrxTakeArgs &a, uint64_t i, uint64_t k, F carries) {
+    const BrxTakeRec r = brx_take_record(mem, a, i, k);
     if (r.len > BRX_MB_MAX_KEY) return BRX_MB_F_LONG_KEY;
     const uint32_t L = (uint32_t)r.len;
     // (wide loads stay inside the STREAM, not only inside the arena: its bounds stand where brx_take_fetch takes the arena's)
-    const uint8_t *p = x.a.out + r.src, *lo_a = x.a.out + x.a.out_off[i], *hi_a = lo_a + x.a.len[i];
+    const uint8_t *p = a.out + r.src, *lo_a = a.out + a.out_off[i], *hi_a = lo_a + a.len[i];
     uint64_t blank = 0, bs = 0, qt = 0;
 #define BRX_MB_KEY_UNIT(g)                                                                                           \
     if (L > 16u * (g)) {                                                                                              \
@@ -190,16 +193,29 @@ BRX_TAKE_HD uint32_t brx_mb_member(M &mem, const BrxMbArgs &x, const BrxMbNames 
     const BrxTake128 b0 = brx_take_place(brx_take_fetch(mem, p + lo + 1u, n0, lo_a, hi_a), 0u, n0);
     BrxTake128 b1 = {0, 0};
     if (bn > 16u) b1 = brx_take_place(brx_take_fetch(mem, p + lo + 17u, bn - 16u, lo_a, hi_a), 0u, bn - 16u);
-    const uint64_t j = x.line_off[i] + line;
-    if (j < line || j >= x.m) return flags;
-    // (not unrolled: the names stay in the launch arguments and are fetched by the scalar unit, one name per turn, instead of all
-    // 8 x 32 bytes living in scalar registers across the walk)
-#pragma unroll 1
-    for (uint32_t q = 0; q < nm.n; q++) {
-        if (nm.len[q] == bn && nm.w[q][0] == b0.lo && nm.w[q][1] == b0.hi && nm.w[q][2] == b1.lo && nm.w[q][3] == b1.hi)
-            mem.max64(x.sel_rec + (uint64_t)q * x.m + j, k + 1u);
-    }
+    const BrxMbKey ky = {bn, b0, b1};
+    carries(ky);
     return flags;
+}
+// the key carries name q
+BRX_TAKE_HD bool brx_mb_key_is(const BrxMbNames &nm, uint32_t q, const BrxMbKey &ky) {
+    return nm.len[q] == ky.bn && nm.w[q][0] == ky.b0.lo && nm.w[q][1] == ky.b0.hi && nm.w[q][2] == ky.b1.lo && nm.w[q][3] == ky.b1.hi;
+}
+
+// The member whose ':' is boundary k of stream i, in line `line`: its key record against the names.  Returns the flag bits it adds
+// to its line.
+template <class M>
+BRX_TAKE_HD uint32_t brx_mb_member(M &mem, const BrxMbArgs &x, const BrxMbNames &nm, uint64_t i, uint64_t k, uint64_t line) {
+    return brx_mb_key(mem, x.a, i, k, [&](const BrxMbKey &ky) {
+        const uint64_t j = x.line_off[i] + line;
+        if (j < line || j >= x.m) return;
+        // (not unrolled: the names stay in the launch arguments and are fetched by the scalar unit, one name per turn, instead of all
+        // 8 x 32 bytes living in scalar registers across the walk)
+#pragma unroll 1
+        for (uint32_t q = 0; q < nm.n; q++) {
+            if (brx_mb_key_is(nm, q, ky)) mem.max64(x.sel_rec + (uint64_t)q * x.m + j, k + 1u);
+        }
+    });
 }
 
 // One lane, one unit: the nv boundaries from k0 on of stream i (c of them count), with `line` and depth `d` in front of the unit.

@@ -316,5 +316,21 @@ inline void elements_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out
                            el_off, total, el_stream, el_rec, el_kind, stream) != BRX_SUCCESS)
         throw std::runtime_error(std::string("brx_elements_batch: ") + brx_last_error());
 }
+// The named members of the nested JSON objects whose openers (sel_stream, sel_rec) name -- a column of member_batch's output or
+// elements_batch's el_stream / el_rec, sel_rec the boundary of the '{'; entries that are no such opener may stay in it.  names (host
+// memory) as for member_batch.  Entry (q, j) at q * m + j is the last member of object j whose key is name q: mem_stream / mem_rec as
+// the record calls take them, mem_kind BRX_MEMBER_MISSING ... BRX_MEMBER_BAD (OBJECT: again an opener for this call; ARRAY: one for
+// elements_batch); n_members[j], status[j] (BRX_OBJECT_OK ... BRX_OBJECT_MISMATCH), end[j] (the closer's boundary) and obj_flags[j]
+// (BRX_MEMBER_LONG_KEY | _ESCAPED_KEY) may each be nullptr.  n_names = 0 is the extent mode: n_members, status and end alone.
+inline void object_batch(brx_ctx *ctx, const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                         const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                         const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m, const uint8_t *names, const uint32_t *name_len,
+                         uint32_t n_names, uint64_t *n_members, uint8_t *status = nullptr, uint64_t *end = nullptr,
+                         uint32_t *mem_stream = nullptr, uint64_t *mem_rec = nullptr, uint8_t *mem_kind = nullptr,
+                         uint8_t *obj_flags = nullptr, void *stream = nullptr) {
+    if (brx_object_batch(ctx, out, out_off, len, n, span, count, pos_off, pos, what, n_pos, sel_stream, sel_rec, m, names, name_len, n_names,
+                         n_members, status, end, mem_stream, mem_rec, mem_kind, obj_flags, stream) != BRX_SUCCESS)
+        throw std::runtime_error(std::string("brx_object_batch: ") + brx_last_error());
+}
 
 } // namespace brotli

@@ -986,7 +986,7 @@ int brx_unescape_batch(brx_ctx *ctx,
  * NULL in count mode; then n = 0 returns BRX_SUCCESS, no launch; then out_off, len, count or pos_off NULL; pos or what NULL with
  * n_pos > 0; span, m or n_pos out of range of one launch (the bound on m keeps n_names * m in range too).
  * Not in scope: paths into nested values, and the extent of a nested value (of a nested array, with its elements: brx_elements_batch
- * below); resolving escapes in keys; names longer than 32 bytes or
+ * below; of a nested object, with its named members: brx_object_batch below that); resolving escapes in keys; names longer than 32 bytes or
  * more than 8 names; validating JSON; pretty-printed JSON with line feeds inside an object; any change to brx_index_set_batch or to
  * the record calls.
  * Count mode reads `what` once, fill mode twice, plus the key records of the depth-1 members; no reference counterpart. */
@@ -1067,7 +1067,8 @@ int brx_member_batch(brx_ctx *ctx,
  * of el_off / el_stream / el_rec / el_kind; n_elem NULL in count mode; then m = 0 returns BRX_SUCCESS, no launch; then sel_stream
  * NULL; out_off, len, count or pos_off NULL with n > 0; pos or what NULL with n_pos > 0; span, m, n_pos or total out of range of one
  * launch.
- * Not in scope: objects ('{' gives NOT_ARRAY: the members of a nested object are the next verb); paths; validating JSON;
+ * Not in scope: objects ('{' gives NOT_ARRAY: the members of a nested object are the next verb, brx_object_batch below); paths;
+ * validating JSON;
  * pretty-printed JSON with line feeds inside an array; any change to brx_index_set_batch, brx_member_batch or the record calls.
  * Reads `what` behind every opener up to its stop, once per call, and record r + 1 of the arrays whose closer stands at r + 1; no
  * reference counterpart.  An array that has not ended 64 boundaries behind its opener is taken by its whole wavefront, 1024
@@ -1085,6 +1086,89 @@ int brx_elements_batch(brx_ctx *ctx,
                        uint64_t *n_elem, uint8_t *status, uint64_t *end,
                        const uint64_t *el_off, uint64_t total, uint32_t *el_stream, uint64_t *el_rec, uint8_t *el_kind,
                        void *hip_stream);
+
+/* ---- the named members of nested JSON objects as selections for the record calls (device memory only) ----------------
+ * brx_member_batch answers kind = BRX_MEMBER_OBJECT and sel_rec = the boundary of the '{' for "meta":{"lang":"en","score":0.93}, and
+ * brx_elements_batch answers BRX_MEMBER_OBJECT for every object of "items":[{"id":1,"price":2.5},...]; there the pipeline ended.  This
+ * pass takes it from there: for a selection of object openers it gives, per requested name, the (stream, record) pair and the kind of
+ * the member's value, and per object the number of members and the closing bracket (the extent of the nested value).  Its input is
+ * what member and elements emit, its output what they and the record calls take: a path a.b.c is member, object, object; an array of
+ * objects is member, elements, object, parse.
+ * out ... n_pos are exactly as for brx_elements_batch: the tables of a fill-mode brx_index_set_batch call at { } [ ] : , and the line
+ * feed, quote '"', escape '\'.  (sel_stream, sel_rec) is a pairs-mode selection of m openers: sel_rec = the boundary index of the
+ * '{'.  A whole column of member's output, or elements' el_stream / el_rec, may be passed with the entries that are no object left in.
+ *   names, name_len   HOST memory, whatever the other pointers are, read before the call returns, exactly as for brx_member_batch:
+ *             name q is names[32 q .. 32 q + name_len[q]); 0 <= n_names <= BRX_MEMBER_MAX_NAMES = 8, 1 <= name_len[q] <=
+ *             BRX_MEMBER_MAX_NAME = 32, no name twice.  They travel to the kernel as launch arguments: no upload, and the call stays
+ *             enqueue-only.  n_names = 0 is the EXTENT MODE: n_members, status and end alone.
+ * Everything else is DEVICE memory.
+ * THE RULE.  Boundary k of stream i, w_k and C(i) = min(count[i], n_pos - pos_off[i]) (0 where pos_off[i] >= n_pos), the boundaries
+ * that count, are as in brx_member_batch's RULE.  Nothing at or behind n_pos is loaded, neither from what nor from pos.  Entry j has
+ * i = sel_stream[j], r = sel_rec[j].
+ *   BRX_OBJECT_NONE.  i >= n or r >= C(i): n_members = 0, end = UINT64_MAX.  Member's MISSING (sel_rec = UINT64_MAX) lands here.
+ *   BRX_OBJECT_NOT_OBJECT.  w_r is not '{': n_members = 0, end = UINT64_MAX.
+ *   THE WALK.  Otherwise k = r + 1, r + 2, ... with the relative depth e = 1.  '{' and '[' give e += 1.  '}' and ']' give e -= 1; at
+ *       e = 0 the object ends at k: status BRX_OBJECT_OK for '}', BRX_OBJECT_MISMATCH for ']', end = k.  A '\n' boundary stops the walk
+ *       (BRX_OBJECT_UNCLOSED, end = k), as does k = C(i) (BRX_OBJECT_UNCLOSED, end = C(i)).  Every other byte is neutral.  The members
+ *       seen before the stop stand.
+ *   A MEMBER is a ':' boundary k met with e = 1; n_members counts them.  Its KEY RECORD (record k of the stream under
+ *       BRX_TAKE_NO_DELIM with D = 1), the trim of 0x20, 0x09 and 0x0D, "carries name q" (bytewise, no escape is resolved), the limit of
+ *       BRX_MEMBER_MAX_KEY = 64 bytes before trimming and the backslash flag are word for word brx_member_batch's.
+ *   VALUE of the member at k: mem_rec = k + 1, and its kind follows from w_{k+1} as in member's RULE: ',' or '}': BRX_MEMBER_SCALAR,
+ *       the value is record k + 1.  '{': BRX_MEMBER_OBJECT, again an opener for this call.  '[': BRX_MEMBER_ARRAY, an opener for
+ *       brx_elements_batch.  Anything else -- a '\n', a ']', k + 1 = C(i) -- BRX_MEMBER_BAD.
+ *   LAST WINS among the members of the walk, as json.loads has it with duplicates.  None carries name q: mem_kind = BRX_MEMBER_MISSING
+ *       and mem_rec = UINT64_MAX, which selects nothing.  mem_stream is sel_stream[j] in every case, whatever it is.
+ *   Results are column-major: entry (q, j) is at index q * m + j, so one name's column is a contiguous selection for a record call or
+ *   for this one.  Every slot with j < m is written, for NONE and NOT_OBJECT entries too; nothing at or beyond n_names * m is written.
+ *   obj_flags[j] (optional): BRX_MEMBER_LONG_KEY | BRX_MEMBER_ESCAPED_KEY over the entry's own members only (0 for NONE and
+ *       NOT_OBJECT).  n_members, status and end are each optional; with n_names = 0, n_members is required.
+ * Nothing outside the bounds that brx_member_batch's contract names is ever loaded.  Stale or garbage tables give wrong members,
+ * never a load or a store outside these bounds.
+ * Check values; stream between brackets, names a, b, c, u, x where not said otherwise, then the status, n_members, end, the names
+ * found as name KIND mem_rec (the others MISSING) and obj_flags:
+ *   [{"u":{"a":1,"b":[2,3],"a":4},"a":5}] r 2: OK members 3 end 11; a SCALAR 11 b ARRAY 6 flags 0
+ *   [{"u":{"a":1,"b":[2,3],"a":4},"a":5}] r 0: OK members 2 end 14; a SCALAR 14 u OBJECT 2 flags 0
+ *   [{"a":{}}] r 2: OK members 0 end 3 flags 0
+ *   [{"a":{"b":1]}] r 2: MISMATCH members 1 end 4; b BAD 4 flags 0
+ *   [{"a":{"b":1,"c":2\n] r 2: UNCLOSED members 2 end 6; b SCALAR 4 c BAD 6 flags 0
+ *   [{"a":{"b":] r 2: UNCLOSED members 1 end 4; b BAD 4 flags 0
+ *   [{"a":{"x":{"b":1},"b":2}}] r 2: OK members 2 end 9; b SCALAR 9 x OBJECT 4 flags 0
+ *   [{"a":{"x":{"b":1},"b":2}}] r 4: OK members 1 end 6; b SCALAR 6 flags 0
+ *   [{"items":[{"id":1},{"id":2}]}] r 3: OK members 1 end 5; id SCALAR 5 flags 0   (name id)
+ *   [{"items":[{"id":1},{"id":2}]}] r 7: OK members 1 end 9; id SCALAR 9 flags 0   (name id)
+ *   [{"a":{<30 x 20>"<32 x k>":1}}] r 2: OK members 1 end 4; k32 SCALAR 4 flags 0   (name k32 = 32 x k; a key record of 64 bytes)
+ *   [{"a":{<31 x 20>"<32 x k>":1}}] r 2: OK members 1 end 4 flags 1   (name k32 = 32 x k; a key record of 65 bytes)
+ *   [{"a":{"a\u0062":1}}] r 2: OK members 1 end 4 flags 2   (name ab)
+ *   [{"a":[1]}] r 2: NOT_OBJECT flags 0
+ *   [{"a":[1]}] r 9: NONE flags 0
+ * hip_stream NULL = the context's own stream and the call returns when the results are there; otherwise it is enqueued, and behind
+ * brx_index_set_batch, brx_member_batch and brx_elements_batch calls on the same stream it needs no synchronisation in between.  The
+ * context's lock is held to enqueue only.  One launch, no scratch of the context's.
+ * BRX_ERR_INVALID_ARGUMENT, checked in this order before anything touches HIP: ctx NULL; n_names above 8; names or name_len NULL with
+ * n_names > 0; a name_len of 0 or above 32; a name twice; only one of sel_stream / sel_rec; with n_names > 0 any of mem_stream /
+ * mem_rec / mem_kind NULL; with n_names = 0 any of them or obj_flags given, or n_members NULL; then m = 0 returns BRX_SUCCESS, no
+ * launch; then sel_stream NULL; out_off, len, count or pos_off NULL with n > 0; pos or what NULL with n_pos > 0; span, m or n_pos
+ * out of range of one launch (the bound on m keeps n_names * m in range too).
+ * Not in scope: enumerating every member of an object; resolving escapes in keys; more than 8 names or names above 32 bytes;
+ * validating JSON; pretty-printed JSON with line feeds inside an object; a single-call path syntax; any change to
+ * brx_index_set_batch, brx_member_batch, brx_elements_batch or the record calls.
+ * Reads `what` behind every opener up to its stop, once per call, and the key records of the object's own members (none in extent
+ * mode); no reference counterpart.  An object that has not ended 64 boundaries behind its opener is taken by its whole wavefront,
+ * 1024 boundaries per step. */
+#define BRX_OBJECT_OK         0u /* the object ended at a '}' */
+#define BRX_OBJECT_NONE       1u /* the entry selects no boundary that counts */
+#define BRX_OBJECT_NOT_OBJECT 2u /* the boundary is not a '{' */
+#define BRX_OBJECT_UNCLOSED   3u /* a line feed or the stream's end came first */
+#define BRX_OBJECT_MISMATCH   4u /* the object ended at a ']' */
+int brx_object_batch(brx_ctx *ctx,
+                     const uint8_t *out, const uint64_t *out_off, const uint64_t *len, uint32_t n, uint64_t span,
+                     const uint64_t *count, const uint64_t *pos_off, const uint64_t *pos, const uint8_t *what, uint64_t n_pos,
+                     const uint32_t *sel_stream, const uint64_t *sel_rec, uint64_t m,
+                     const uint8_t *names, const uint32_t *name_len, uint32_t n_names,
+                     uint64_t *n_members, uint8_t *status, uint64_t *end,
+                     uint32_t *mem_stream, uint64_t *mem_rec, uint8_t *mem_kind, uint8_t *obj_flags,
+                     void *hip_stream);
 
 /* ---- Read-shaped stream facade (one object = one stream, like one reference Decompressor) ----------
  * brx_stream_new copies the compressed bytes and queues the stream on its context.  The first brx_stream_read of
