@@ -453,23 +453,35 @@ def _nbltypes(b, n):
         b.put(1, 1); b.put(k, 3); b.put(n - 1 - (1 << k), k)
 
 
-def incomplete_code_stream(kind, pad_ones=64):
+def incomplete_code_stream(kind, pad_ones=64, category="L", info=None):
     """Q15: an under-subscribed complex prefix code is accepted when it is built; reading one of its unassigned codewords
     fails later with the error of the place that reads it.  kind -> expected status:
       'literal' 21 ParseErrorInsertLiterals, 'iac' 20 ParseErrorInsertAndCopyLength, 'distance' 19 ParseErrorDistanceCode,
       'context_map' 17 ParseErrorContextMap, 'block_type' 5 InvalidBlockSwitchCommandCode,
-      'block_count' 24 UnexpectedEOF (parse_block_count maps Ok(None) to UnexpectedEOF, src/lib.rs:977).
-    pad_ones: one-bits after the bad codeword (enough of them: the failure is "no such codeword", not end of input)."""
+      'block_count' 24 UnexpectedEOF (parse_block_count maps Ok(None) to UnexpectedEOF, src/lib.rs:977),
+      'type_beyond' 8 InvalidSymbol: three block types, and a simple block type code that names symbol 6 of an alphabet of 5.
+    pad_ones: one-bits after the bad codeword (enough of them: the failure is "no such codeword", not end of input).
+    category: which of "L", "I", "D" has the block types of the three block kinds (the first count is 1: the switch stands in front
+    of the category's second symbol -- the second literal, the second command, the second distance);  info: a dict that
+    receives 'model', the output of the commands in front of the bad codeword."""
     b = Bits()
     stream_header(b, 16)
     _mb_header(b, 16)
-    two_l = kind in ("block_type", "block_count")
-    if two_l:
-        _nbltypes(b, 2)
+    switching = kind in ("block_type", "block_count", "type_beyond")
+    nbl = {c: 1 for c in "LID"}
+    if switching:
+        nbl[category] = 3 if kind == "type_beyond" else 2
+    types = counts = None
+    for c in "LID":
+        n = nbl[c]
+        _nbltypes(b, n)
+        if n == 1:
+            continue
         if kind == "block_type":
-            types = complex_code(b, [1, 2, 0, 0])          # '11' unassigned
+            types = complex_code(b, [1, 2, 0, 0])           # '11' unassigned
+        elif kind == "type_beyond":
+            simple_code(b, [1, 6], 3)                       # alphabet NBLTYPES + 2 = 5 -> 3 bits per symbol: 6 is not in it
         else:
-            types = None
             simple_code(b, [0, 1], 2)                       # alphabet NBLTYPES + 2 = 4 -> 2 bits per symbol
         if kind == "block_count":
             counts = complex_code(b, [1, 2] + [0] * 24)     # '11' unassigned
@@ -477,12 +489,8 @@ def incomplete_code_stream(kind, pad_ones=64):
         else:
             simple_code(b, [0], 5)                          # alphabet 26 -> 5 bits; one symbol: zero bits per lookup
         b.put(0, 2)                                         # extra bits of count symbol 0: block length 1
-    else:
-        _nbltypes(b, 1)
-    _nbltypes(b, 1)
-    _nbltypes(b, 1)
     b.put(0, 2); b.put(0, 4)                                # NPOSTFIX, NDIRECT
-    for _ in range(2 if two_l else 1):
+    for _ in range(nbl["L"]):
         b.put(0, 2)                                         # context modes
     if kind == "context_map":
         _nbltypes(b, 2)                                     # NTREESL = 2
@@ -495,14 +503,26 @@ def incomplete_code_stream(kind, pad_ones=64):
     _nbltypes(b, 1)                                         # NTREESD
     lit = complex_code(b, [8] * 255 + [0] if kind == "literal" else [8] * 256)
     sym, ie, ce = iac_symbol(2, 4)
-    if kind == "iac":
-        iac = complex_code(b, [0] * sym + [1, 2] + [0] * (704 - sym - 2), zero_run_17=True)
-    else:
-        iac = complex_code(b, uniform_lengths(704, [sym, sym + 1]), zero_run_17=True)
+    for _ in range(nbl["I"]):
+        if kind == "iac":
+            iac = complex_code(b, [0] * sym + [1, 2] + [0] * (704 - sym - 2), zero_run_17=True)
+        else:
+            iac = complex_code(b, uniform_lengths(704, [sym, sym + 1]), zero_run_17=True)
     if kind == "distance":
         dist = complex_code(b, [1, 2] + [0] * 62, zero_run_17=True)
     else:
         dist = complex_code(b, uniform_lengths(64))
+
+    def bad_switch():
+        if kind == "block_type":
+            b.put(3, 2)                                     # bad type code
+        elif kind == "block_count":
+            put_sym(b, {0: (0, 1), 1: (1, 1)}, 1)           # type code 1 = next block type (simple code: 1 bit)
+            b.put(3, 2)                                     # then the block count: unassigned codeword
+        else:
+            b.put(1, 1)                                     # (type_beyond: the header is refused before this is read)
+
+    model = b""
     if kind == "iac":
         b.put(3, 2)
     else:
@@ -512,14 +532,25 @@ def incomplete_code_stream(kind, pad_ones=64):
             b.put(0xFF, 8)                                  # codeword 11111111 = the absent 256th symbol
         else:
             put_sym(b, lit, 65)                             # first literal; its block count (1) is used up
-            if kind == "block_type":
-                b.put(3, 2)                                 # block switch before the second literal: bad type code
-            elif kind == "block_count":
-                put_sym(b, {0: (0, 1), 1: (1, 1)}, 1)       # type code 1 = next block type (simple code: 1 bit)
-                b.put(3, 2)                                 # then the block count: unassigned codeword
+            model = b"A"
+            if switching and category == "L":
+                bad_switch()                                # block switch before the second literal
+            elif switching:
+                # the first command whole: the second literal, distance 1 (code 16, one extra bit), a copy of 4 ...
+                put_sym(b, lit, 66)
+                put_sym(b, dist, 16); b.put(0, 1)
+                model = b"ABBBBB"
+                if category == "D":                         # ... the second command up to its distance symbol
+                    put_sym(b, iac, sym)
+                    b.put(*ie); b.put(*ce)
+                    put_sym(b, lit, 67); put_sym(b, lit, 68)
+                    model += b"CD"
+                bad_switch()                                # in front of the second command / the second distance
             elif kind == "distance":
                 put_sym(b, lit, 66)
                 b.put(3, 2)
+    if info is not None:
+        info["model"] = model
     b.put((1 << pad_ones) - 1, pad_ones)
     return b.bytes()
 
@@ -801,7 +832,9 @@ def many_trees_stream(seed, ntl, ntd, nbl_l, nbl_d, n_cmds=400, wbits=18, rlemax
     then a copy of 2 .. 5 (all four distance contexts).  The caller takes the expected output from the oracle (the stream is
     valid by construction: a model of the distance ring keeps every distance inside the output).  rlemax / imtf: the context maps
     are sent that way (context_map);  mode: the literal context mode (default: drawn);  dmap: the distance context map;  info: a
-    dict that receives what was emitted -- mode, cmap_l, cmap_d, and dist_ctx_trees, the (distance context, tree) pairs used."""
+    dict that receives what was emitted -- mode, cmap_l, cmap_d, and dist_ctx_trees, the (distance context, tree) pairs used.
+    Anything beyond its two count codes and two type symbols -- insert&copy block types, explicit type symbols, the other 24 count codes,
+    block types of different context modes -- is built by switch_cases.MetaBlock."""
     rng = random.Random(seed)
     b = Bits()
     stream_header(b, wbits)
