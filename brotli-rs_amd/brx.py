@@ -213,7 +213,7 @@ def status_str(code: int) -> str:
 # brx_ctx_set_option (include/brx.h, BRX_OPTION_*): explicit knobs -- neither the library nor this module reads the environment
 OPTIONS = {"command_loop": 1, "loop_build": 2, "queue_order": 3, "hand_up": 4, "levels": 5, "tiny_bytes": 6,
            "host_in_place": 7, "grid_cap": 8, "small_bytes": 9, "small_waves": 10, "trace": 11, "reader_window": 12, "level4": 13, "reader_mb_room": 14,
-           "reader_batch": 15}
+           "reader_batch": 15, "prio_shift": 16}
 
 
 def _on(stream):
@@ -1051,7 +1051,8 @@ class Context:
         return int(self._lib.brx_last_timing(self._h, 7))
 
     def last_trace(self, n):
-        """(n, 4) uint64: start, end (100 MHz realtime), HW_ID | level << 32, workgroup | grid << 32 per stream (option trace = 1)."""
+        """(n, 4) uint64: start, end (100 MHz realtime), place | level << 32, workgroup | grid << 32 per stream (option trace = 1).
+        place: HW_ID[15:0] | XCC_ID << 16 | the wave's rank in the priority rotation << 20 | option prio_shift << 24 (include/brx.h)."""
         import numpy as np
         buf = np.zeros((n, 4), dtype=np.uint64)
         rc = self._lib.brx_last_trace(self._h, buf.ctypes.data, n)

@@ -194,6 +194,7 @@ struct brx_ctx {
     uint32_t debug_stop = 0;
     bool debug_stats = false, debug_stats_all = false, no_order = false, no_mirror = false;
     int loop_build = -1; // -1 = by occupancy (launch()); bring-up: BRX_LOOP_BUILD forces 0 / 1
+    uint32_t prio_shift = BRX_PRIO_SHIFT_DEFAULT; // BRX_OPTION_PRIO_SHIFT: issue priority by turns (BrxKernelArgs::prio_shift)
     uint32_t dump_interval = 0, dump_max = 0; // BRX_DEBUG_DUMP=interval:max:path (with BRX_DEBUG_STOP=9)
     std::string dump_path;
     // host-mode device staging (grown on demand)
@@ -484,22 +485,30 @@ extern "C" int brx_ctx_create(brx_ctx **out, int device) {
 
 static void stream_detach(brx_stream *s);
 
+// What brx_ctx_set_option refuses for `value`, or nullptr: the options with a range, in one place.  It needs no context (and no
+// device), so the values are checked first -- for every option alike.
+static const char *option_value_refused(uint32_t option, int64_t value) {
+    switch (option) {
+    case BRX_OPTION_COMMAND_LOOP: return value != 0 && value != 6 && value != 7 && value != 8 ? "brx_ctx_set_option: command loop is 0, 6, 7 or 8" : nullptr;
+    case BRX_OPTION_LOOP_BUILD: return value < -1 || value > 1 ? "brx_ctx_set_option: loop build is -1, 0 or 1" : nullptr;
+    case BRX_OPTION_LEVELS: return value < 0 || value > 2 ? "brx_ctx_set_option: levels is 0, 1 or 2" : nullptr;
+    case BRX_OPTION_READER_BATCH: return value != 0 && value != 1 ? "brx_ctx_set_option: reader batch is 0 or 1" : nullptr;
+    case BRX_OPTION_READER_WINDOW: return value < (1 << 20) || value > (256 << 20) ? "brx_ctx_set_option: reader window is 1 MiB .. 256 MiB" : nullptr;
+    case BRX_OPTION_PRIO_SHIFT: return value < 0 || value > 31 ? "brx_ctx_set_option: prio shift is 0 .. 31" : nullptr;
+    default: return nullptr;
+    }
+}
+
 extern "C" int brx_ctx_set_option(brx_ctx *c, uint32_t option, int64_t value) {
+    if (const char *why = option_value_refused(option, value)) return fail(BRX_ERR_INVALID_ARGUMENT, why);
     if (!c) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: ctx is NULL");
     std::lock_guard<std::mutex> lk(c->mu);
     switch (option) {
-    case BRX_OPTION_COMMAND_LOOP:
-        if (value != 0 && value != 6 && value != 7 && value != 8) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: command loop is 0, 6, 7 or 8");
-        c->debug_stop = (uint32_t)value;
-        break;
-    case BRX_OPTION_LOOP_BUILD:
-        if (value < -1 || value > 1) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: loop build is -1, 0 or 1");
-        c->loop_build = (int)value;
-        break;
+    case BRX_OPTION_COMMAND_LOOP: c->debug_stop = (uint32_t)value; break;
+    case BRX_OPTION_LOOP_BUILD: c->loop_build = (int)value; break;
     case BRX_OPTION_QUEUE_ORDER: c->no_order = value == 0; break;
     case BRX_OPTION_HAND_UP: c->no_defer = value == 0; break;
     case BRX_OPTION_LEVELS:
-        if (value < 0 || value > 2) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: levels is 0, 1 or 2");
         c->no_plan_b = value == 0;
         c->force_plan_b = value >= 2;
         break;
@@ -510,15 +519,10 @@ extern "C" int brx_ctx_set_option(brx_ctx *c, uint32_t option, int64_t value) {
     case BRX_OPTION_TRACE: c->trace_on = value != 0; break;
     case BRX_OPTION_LEVEL4: c->level4 = value != 0; break;
     case BRX_OPTION_READER_MB_ROOM: c->reader_mb_room = value != 0; break;
-    case BRX_OPTION_READER_BATCH:
-        if (value != 0 && value != 1) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: reader batch is 0 or 1");
-        c->reader_batch = value != 0;
-        break;
-    case BRX_OPTION_READER_WINDOW:
-        if (value < (1 << 20) || value > (256 << 20)) return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: reader window is 1 MiB .. 256 MiB");
-        c->reader_window = ((size_t)value + 65535u) & ~(size_t)65535;
-        break;
+    case BRX_OPTION_READER_BATCH: c->reader_batch = value != 0; break;
+    case BRX_OPTION_READER_WINDOW: c->reader_window = ((size_t)value + 65535u) & ~(size_t)65535; break;
     case BRX_OPTION_SMALL_WAVES: c->small_waves_per_cu = (uint32_t)std::min<int64_t>(std::max<int64_t>(value, 1), 32); break;
+    case BRX_OPTION_PRIO_SHIFT: c->prio_shift = (uint32_t)value; break;
     default: return fail(BRX_ERR_INVALID_ARGUMENT, "brx_ctx_set_option: unknown option");
     }
     return BRX_SUCCESS;
@@ -708,6 +712,7 @@ static int launch(brx_ctx *c, hipStream_t st, const LaunchReq &r) {
     // which build of the command loop (brx_hot.S): with at most BRX_SW_WAVES_PER_CU streams per CU the CU's scalar ALU has
     // room and the build with the shorter dependent chain wins; fuller CUs take the one that spares the scalar ALU
     a.loop_build = c->loop_build >= 0 ? (uint32_t)c->loop_build : (grid <= c->max_grid / 16u * BRX_SW_WAVES_PER_CU ? 1u : 0u);
+    a.prio_shift = c->prio_shift;
     const size_t ring_slot = (size_t)(c->launch_seq++ % BRX_COUNTER_RING);
     // one 128-B line per launch; a reader round -- hundreds of ms on a HIP stream of its own while batches go on -- has a line of its own
     // that no later launch can take over (rounds run one at a time)

@@ -117,7 +117,18 @@
 #define LBLEN s65
 #define IBLEN s66
 #define DBLEN s67
-#define PRIOW s60                // wave slot in the SIMD
+#define PRIOW s60                // issue priority by turns (.Lspecial): bits 4:0 = the clock's shift, bits 9:8 = this wave's rank
+// CLK: the shared clock at a roll of the staging (.Lspecial only), the destination of a scalar LOAD: between its s_memrealtime and
+// the s_waitcnt lgkmcnt(0) behind it nothing may read or write the pair.
+#ifdef BRX_WIN_SGPR
+#define CLK s[84:85]            // = T0 / T1 THEMSELVES in this build (T1 does not survive a refill here, so .Lspecial may take it):
+#define CLKLO s84               // an instruction that uses T0 or T1 between the s_memrealtime and its wait in .Lspecial races the load
+#define CLKHI s85
+#else
+#define CLK s[58:59]            // = NXT's pair, which this build never uses (it keeps no window in SGPRs); T1 stays live across a refill here
+#define CLKLO s58
+#define CLKHI s59
+#endif
 #define RUN s68                 // literals left in the current run, one behind
 #define NXT s[58:59]            // the next dword of the staged input (lane WL of chunk A), zero-extended
 #define NXTLO s58
@@ -409,21 +420,23 @@
 #ifndef TAIL_PAD_NOPS
 #define TAIL_PAD_NOPS 0
 #endif
-.macro STUB_PAD
+.macro STUB_PAD cut=0
 #ifndef BRX_WIN_SGPR
-    .rept STUB_PAD_NOPS
+    .if STUB_PAD_NOPS > \cut
+    .rept STUB_PAD_NOPS - \cut
     s_nop 0
     .endr
+    .endif
 #endif
 .endm
 // Out-of-line part of a refill: next dword of the staged input (lane WL of chunk A) enters the window.
-.macro REFILL_STUB id
+.macro REFILL_STUB id, cut=0
 .Lrf_stub_\id:
     REFILL_CORE
     s_cbranch_scc1 .Lrf_back_\id
     s_call_b64 LINKA, .Lspecial
     s_branch .Lrf_back_\id
-    STUB_PAD
+    STUB_PAD \cut
 .endm
 // A register-resident tree keeps its limits as COUNTS -- lane L: limit[L] in units of L-bit codes (first_code + count), the
 // header word >> (31 - L) -- so that its compare works on the candidate index the lane computes anyway (the top L bits of
@@ -582,7 +595,6 @@
 .endm
 // ======================================================================================================== entry
     .p2align 8
-    s_getreg_b32 PRIOW, hwreg(HW_REG_HW_ID, 0, 4)       // this wave's slot in its SIMD (phase of the priority rotation, .Lspecial)
     s_waitcnt vmcnt(0) lgkmcnt(0)
     v_mov_b32 VZERO, 0
     v_mbcnt_lo_u32_b32 VLANE, -1, 0
@@ -671,8 +683,11 @@
     ds_read_b64 v[32:33], VZERO offset:LDS_MBW+32       // ntl, ntd
     ds_read_b32 v36, VZERO offset:LDS_MBW+124           // MBW_ASM: 1 | mixed context modes << 1
     ds_read_b32 v37, VZERO offset:LDS_MBW+156           // MBW_WSAFE
+    ds_read_b32 v34, VZERO offset:LDS_ST+188            // ST_SPEC: bits 12:8 = the clock's shift, bits 17:16 = this wave's rank (.Lspecial)
     s_waitcnt lgkmcnt(0)
     v_readfirstlane_b32 FLAGS, v36
+    v_readfirstlane_b32 PRIOW, v34
+    s_lshr_b32 PRIOW, PRIOW, 8
     // Where the loop gets poisoned (.Lspecial): the dispatcher says (mbw[MBW_WSAFE], round 6).  The resumable decode of the bounded
     // reader, which cannot take anything back: END_MARGIN dwords in front of the end of the input, every bit consumed here is a real
     // bit.  Batches: four dwords BEHIND the end -- a valid stream's last meta-block ends before that (the staged input repeats the
@@ -2179,18 +2194,26 @@
     s_add_u32 CBASE, CBASE, 64
     s_add_u32 T0, CBASE, 64
     v_add_u32 VT4, T0, VLANE
+    s_memrealtime CLK                                   // (a scalar load: it returns under the roll; nothing touches CLK before the wait)
     v_min_u32 VT4, WENDM1, VT4
     v_lshlrev_b32 VT4, 2, VT4
     global_load_dword VCHB, VT4, INP
     s_mov_b64 exec, XLOOP
     s_mov_b32 WL, 0
     WIN_ROLLED
-    // Issue priority by turns.  The arbiter of a SIMD serves its oldest wave first, and with the CU's scalar ALU saturated
-    // (16 streams per CU) that starves the youngest waves: the oldest streams finish in 8.1 ms, the youngest in 11.0, and
-    // a launch takes as long as its slowest wave.  Every 256 bytes of input a wave takes the next of the four priority
-    // levels, offset by its slot in the SIMD, so that over a stream every wave spends the same time at every level.
-    s_lshr_b32 T0, CBASE, 6
-    s_add_u32 T0, T0, PRIOW
+    // Issue priority by turns.  The arbiter of a SIMD serves the highest priority first and among equals its OLDEST wave, and with
+    // the CU's scalar ALU saturated (16 streams per CU) that starves the youngest waves: a launch takes as long as its slowest wave.
+    // The level comes from a clock that every wave reads (s_memrealtime, 100 MHz): level = ((clock >> shift) + rank) & 3, taken at
+    // every roll of the staging.  The waves of a SIMD hold ranks that differ mod 4 (their wave slots: the dispatcher), so at every
+    // instant they hold four different levels -- up to the one roll interval a wave keeps its old level behind a boundary -- and
+    // age decides nothing; every wave spends a quarter of the TIME at each level, whatever its stream looks like.  (Until round
+    // 26 the level followed the wave's own position in its input, a step every 256 bytes: waves move at different speeds, two of
+    // them met on one level most of the time, and the same wave lost every such tie -- DESIGN 8.1.)  The shift is the context's
+    // BRX_OPTION_PRIO_SHIFT (31: the level never changes).  Scalar loads return out of order: nothing stays in flight for the loop.
+    s_waitcnt lgkmcnt(0)
+    s_lshr_b64 CLK, CLK, PRIOW                          // (the shift: bits 5:0 of the operand)
+    s_lshr_b32 CLKHI, PRIOW, 8
+    s_add_u32 T0, CLKLO, CLKHI
     s_and_b32 T0, T0, 3
     s_cmp_lt_u32 T0, 2
     s_cbranch_scc1 .Lprio_01
@@ -2226,7 +2249,8 @@
 .Lspecial_ret:
     s_setpc_b64 LINKA
 
-    REFILL_STUB 1
+    REFILL_STUB 1, 4                                    // (.Lspecial grew by four dwords in round 26.  Full-chip build: what lies behind this stub stays
+                                                        // where it was.  Sparse-launch build, no padding: everything behind .Lspecial moves by 16 bytes)
     REFILL_STUB 2
     REFILL_STUB 3
     REFILL_STUB 4

@@ -149,6 +149,15 @@ __shared__ unsigned long long g_prof[32];
 // ---- wave-level primitives ---------------------------------------------------------------------------
 FI u32 rfl(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 FI u32 rdl(u32 v, u32 lane) { return (u32)__builtin_amdgcn_readlane((int)v, (int)lane); }
+// Issue priority by turns, the rule of brx_hot.S (.Lspecial): level = ((realtime clock >> shift) + rank) & 3.  (s_setprio takes an immediate.)
+FI void prio_by_clock(u32 shift, u32 rank) {
+    switch (((u32)(__builtin_amdgcn_s_memrealtime() >> shift) + rank) & 3u) {
+    case 0u: __builtin_amdgcn_s_setprio(0); break;
+    case 1u: __builtin_amdgcn_s_setprio(1); break;
+    case 2u: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
 FI u64 ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 // vec with lane `lane` replaced by the wave-uniform `val` (a compare and a select: gfx9's v_writelane_b32 takes one SGPR
 // operand only, its lane select would have to travel through M0)
@@ -412,6 +421,7 @@ FI u32 in_byte_tail(Dec &d) {
 #define ST_IN_LOW 45   // (2 words) ... or once the input cursor is this far (BrxResume::in_low; else ~0)
 #define ST_SPEC 47    // bit 1: option command_loop = 6 (no meta-block qualifies for the assembly loop); bit 0 = 1: batch decode -- the assembly loop may run past the end of the input (a meta-block that did is taken back and decoded
                       // again by the C++ loop: "speculative end" in the kernel's stream loop); 0: the resumable decode, END_MARGIN applies
+                      // bits 12:8: BrxKernelArgs::prio_shift, bits 17:16: the wave's rank -- what brx_hot.S (.Lspecial) makes its issue priority from
 #define ST_NEED 42    // after a header whose tables spilled: words of table memory the meta-block needs (Dec::need_peak)
 #define SEG_NEED_HEADER 100u // seg_frame: a compressed meta-block follows (anything < 100 is a final status)
 #define SEG_PAUSED 101u      // seg_frame (resumable mode): stopped between two meta-blocks, ST_PAUSE_AT reached
@@ -2347,6 +2357,10 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
         }
     }
 #endif
+    // Issue priority by turns (BrxKernelArgs::prio_shift): this wave's rank among the waves of its SIMD is its wave slot.
+    const u32 hw_id = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
+    const u32 xcc_id = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)); // XCC_ID[3:0] (the trace's)
+    const u32 prio_rank = hw_id & 3u;
     // Work queue.  A wave's FIRST stream is its workgroup index, no atomic: 4096 waves adding to one address from eight
     // XCDs serialise at ~13 ns each (4096 EMPTY streams took 106 us that way, most of what config 3 took).  Later streams
     // come from the counter (queue slot = grid size + ticket).  Measured and dropped: a plain device-scope load of the
@@ -2459,10 +2473,13 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
                 s.st[ST_IACTAB] = (u32)(uintptr_t)a.t.iac; s.st[ST_IACTAB + 1] = (u32)((u64)(uintptr_t)a.t.iac >> 32);
                 s.st[ST_PAUSE_AT] = 0xffffffffu; s.st[ST_PAUSE_AT + 1] = 0xffffffffu;
                 s.st[ST_IN_LOW] = 0xffffffffu; s.st[ST_IN_LOW + 1] = 0xffffffffu;
-                s.st[ST_SPEC] = ((a.resume == nullptr && a.rdesc == nullptr && a.debug_stop == 0u) ? 1u : 0u) | (a.debug_stop == 6u ? 2u : 0u);
+                s.st[ST_SPEC] = ((a.resume == nullptr && a.rdesc == nullptr && a.debug_stop == 0u) ? 1u : 0u) | (a.debug_stop == 6u ? 2u : 0u) |
+                                (a.prio_shift << 8) | (prio_rank << 16);
             }
             if (lane < 32u) s.pad[lane] = 0u;
         }
+        // The phases outside the loop take their turn too: all 16 waves of a CU are in their headers at the same time at a launch's start.
+        prio_by_clock(a.prio_shift, prio_rank);
 #if BRX_LEVEL == 0
         if (a.resume != nullptr || rd != nullptr) {
             // ---- resumable mode: one stream decoded in slices against a sliding output window (brx_api.cpp, streaming
@@ -2492,6 +2509,7 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
                     s.st[29] = 0u; s.st[30] = 0u;
                     const u64 wdl = 8ull * in_len + (u64)cap + 65536ull;
                     s.st[31] = (u32)wdl; s.st[32] = (u32)(wdl >> 32);
+                    s.st[ST_SPEC] = (s.st[ST_SPEC] & 0xffu) | (a.prio_shift << 8) | (prio_rank << 16); // (the record holds an earlier wave's)
                 }
                 phase = rfl(rec->phase);
                 st = (phase == PH_LOOP || phase == PH_ASMEXIT) ? HC_CONTINUE : 0u;
@@ -2864,7 +2882,8 @@ __global__ __launch_bounds__(BRX_WAVE, BRX_WAVES_PER_SIMD) void BRX_KERNEL_NAME(
         if (a.trace != nullptr && lane == 0u) {
             a.trace[(size_t)sid * 4u] = t_begin;
             a.trace[(size_t)sid * 4u + 1u] = __builtin_amdgcn_s_memrealtime();
-            a.trace[(size_t)sid * 4u + 2u] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) | ((unsigned long long)BRX_LEVEL << 32);
+            // (HW_ID's bits 15:0 -- wave slot, SIMD, pipe, CU, SH, SE -- then in place of its upper half: XCC_ID, the wave's rank and the shift)
+            a.trace[(size_t)sid * 4u + 2u] = (unsigned long long)((hw_id & 0xffffu) | (xcc_id << 16) | (prio_rank << 20) | (a.prio_shift << 24)) | ((unsigned long long)BRX_LEVEL << 32);
             a.trace[(size_t)sid * 4u + 3u] = (unsigned long long)blockIdx.x | ((unsigned long long)gridDim.x << 32);
         }
     }

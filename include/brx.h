@@ -125,7 +125,8 @@ int brx_ctx_create(brx_ctx **out, int device);
 void brx_ctx_destroy(brx_ctx *ctx);
 
 /* Tuning and A/B knobs of a context: explicit arguments -- the library reads NO environment variable.  Takes effect for the
- * launches enqueued after the call; unknown options return BRX_ERR_INVALID_ARGUMENT.  The defaults are the measured best; the
+ * launches enqueued after the call; unknown options return BRX_ERR_INVALID_ARGUMENT, and so does a value outside an option's range
+ * (checked first, before the context is looked at).  The defaults are the measured best; the
  * test suite uses these to reach every path (the C++-only command loops, both builds of the assembly loop, the wider kernel
  * instances behind / next to the regular one, the lean instance for short streams). */
 enum {
@@ -158,9 +159,12 @@ enum {
                                      window and lets the buffer grow to window + meta-block (at most ~34 MiB), so that the fast loop runs it
                                      (default); 0 = such meta-blocks decode command by command in the ~22 MiB buffer (~8 x slower): streams
                                      started afterwards */
-    BRX_OPTION_READER_BATCH = 15  /* 1 = the slices of bounded / pulled streams that are asked for at the same time go out together, one launch
+    BRX_OPTION_READER_BATCH = 15, /* 1 = the slices of bounded / pulled streams that are asked for at the same time go out together, one launch
                                      per round (default; brx_stream_advance, and brx_stream_read on many threads); 0 = every slice is a launch
                                      of its own, read back from the device (the A/B switch) */
+    BRX_OPTION_PRIO_SHIFT = 16    /* 0 .. 31: the waves of a SIMD take the four issue
+                                     priorities by turns, level = ((100 MHz realtime clock >> this) + the wave's rank) & 3 -- a level lasts
+                                     2^this x 10 ns (default 16: 655 us); 31 = the levels never change.  Results do not depend on it */
 };
 int brx_ctx_set_option(brx_ctx *ctx, uint32_t option, int64_t value);
 
@@ -222,8 +226,9 @@ const char *brx_last_error(void);
 double brx_last_timing(brx_ctx *ctx, int which);
 
 /* Diagnostics (BRX_OPTION_TRACE = 1): 4 words per stream of the most recent launch -- start and end of its decode on the GPU's
- * 100 MHz realtime counter, HW_ID register (XCC / SE / CU / SIMD / wave slot of the wave that decoded it) | kernel level << 32,
- * workgroup index | grid size << 32.  Streams decoded by the lean instance have all-zero records.  Waits for that launch.
+ * 100 MHz realtime counter, place of the wave that decoded it | kernel level << 32, workgroup index | grid size << 32.  The place:
+ * bits 15:0 of the HW_ID register (wave slot 3:0, SIMD 5:4, pipe 7:6, CU 11:8, SH 12, SE 15:13), XCC_ID in bits 19:16, the wave's
+ * rank in the priority rotation in bits 21:20 and BRX_OPTION_PRIO_SHIFT in bits 28:24.  Streams decoded by the lean instance have all-zero records.  Waits for that launch.
  * While the option is on, the host-pointer path decodes a batch in ONE launch (no chunks on separate HIP streams). */
 int brx_last_trace(brx_ctx *ctx, uint64_t *dst, uint32_t n);
 

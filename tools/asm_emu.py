@@ -503,6 +503,11 @@ class Wave:
             addr = (self.s64(ops[1][1]) + self.ssrc(ops[2]) + i.mods.get("offset", 0)) & ~3
             raw = self.mem_read(addr, 4 * n).view(np.uint32)
             self.queue(self.lg_q, [("s", ops[0][1] + k) for k in range(n)], [int(x) for x in raw], "lg", smem=True)
+        elif op == "s_memrealtime":
+            # the 100 MHz clock all waves share (.Lspecial: issue priority by turns) -- a scalar load like the others (lgkmcnt, out of
+            # order); any value does, the priority has no architectural effect: this wave's cycle count at 2.4 GHz
+            t = self.cycles // 24
+            self.queue(self.lg_q, [("s", ops[0][1]), ("s", ops[0][1] + 1)], [t & MASK32, (t >> 32) & MASK32], "lg", smem=True)
         # ---- VALU
         elif op == "s_set_gpr_idx_on":  # gfx9 VGPR index mode: M0[7:0] = index, imm = which operands it applies to
             self.gpr_idx = (self.ssrc(ops[0]) & 0xFF, ops[1][1] if ops[1][0] == "imm" else 0)

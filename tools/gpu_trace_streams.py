@@ -29,7 +29,9 @@ for T in (0.5, 2, 5, 8, 12, 16, 20, 25, 30, 35, 40):
     on = (st <= T) & (en > T)
     print("t=%5.1f ms resident: " % T + "  ".join("L%d %4d" % (L, int((on & (lv == L)).sum())) for L in range(4)))
 hw = t[:, 2] & np.uint64(0xffffffff)
-# HW_ID gfx9: wave 3:0, simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 (gfx94x: se 14:13?), ... print distinct places early on
+# HW_ID on gfx950 as on gfx9: wave 3:0, simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 -- checked in profiles/r26_prio_trace.txt: SE 0..3,
+# SH 0, CU 0..8, and with XCC_ID (bits 19:16 of the trace word) 1024 places of four waves each in a 4096-wave launch.  tools/gpu_prio_trace.py
+# has the per-SIMD view.
 early = st <= 0.5
 cu = ((hw >> np.uint64(8)) & np.uint64(0xf)).astype(int); se = ((hw >> np.uint64(13)) & np.uint64(7)).astype(int)
 print("streams started within 0.5 ms:", int(early.sum()), "by level", [int((early & (lv == L)).sum()) for L in range(4)])
